@@ -17,6 +17,13 @@ removed; with N>1 the RCCL gradient all-reduce runs eagerly between the two grap
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2]; N>1 under
 torch.distributed.run. Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, print
+the line. --full adds the measurements that take runs of their own after the timed region: the
+roofline of the dominant kernels, the per-entry HIP-event profile of an eager step, the k-NN
+graph build and the CPU baseline (each still governed by --no-kernel-timing, --entries and
+--cpu-seconds). --dump-outputs DIR writes what the last timed step computed (logits, loss,
+gradients, updated parameters) as DIR/<name>.npy, for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -120,9 +127,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2")
     ap.add_argument("--graphs-per-gpu", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the measurements that take runs of their "
+                         "own: roofline of the dominant kernels, per-entry profile, k-NN graph "
+                         "build, CPU baseline (off: the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (logits, loss, "
+                         "gradients, updated parameters; rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="bounded CPU-baseline sample (rank 0, N=1 only); 0 disables")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+                    help="--full: bounded CPU-baseline sample (rank 0, N=1 only); 0 disables")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="--full: skip the HIP-event kernel timings (roofline, entries, k-NN)")
     ap.add_argument("--opt", choices=["lgnn", "fused", "foreach"], default="lgnn",
                     help="Adam implementation, inside the timed step either way: lgnn = one "
                          "HIP launch (lesion_gnn_amd.optim.Adam); fused / foreach = torch's")
@@ -142,8 +157,8 @@ def parse():
                          "all-reduces inside forward and backward), off = per-replica statistics "
                          "(torch DDP's default)")
     ap.add_argument("--entries", type=int, default=1,
-                    help="1: per-entry HIP-event profile of an eager step (rank 0, after the "
-                         "timed region)")
+                    help="--full: 1 = per-entry HIP-event profile of an eager step (rank 0, after "
+                         "the timed region)")
     ap.add_argument("--path-option", action="append", default=[], metavar="NAME=VALUE",
                     help="A/B only: set an lgnn_set_option path option before the run "
                          "(gat_pipe, gat_bpc, graph_sorted; include/lgnn.h LGNN_OPT_*)")
@@ -1013,7 +1028,38 @@ def make_step(plan: tuple, fwd_bwd, bucket, opt, dev, info: dict | None = None):
     return step
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(path, last, model) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, as float32 <name>.npy
+    under `path`: the logits and the loss of its forward, the gradient its backward left on every
+    parameter (after the all-reduce for N > 1) and every parameter after its optimizer step.
+    An array larger than its even share of DUMP_BUDGET_BYTES is cut to a fixed seeded sample of
+    its flattened elements (the same elements for the same shapes)."""
+    import numpy as np
+
+    arrays = {"logits": last["logits"], "loss": last["loss"]}
+    named = [(n[len("_orig_mod."):] if n.startswith("_orig_mod.") else n, p)
+             for n, p in model.named_parameters()]
+    for n, p in named:
+        if p.grad is not None:
+            arrays["grad." + n] = p.grad
+    for n, p in named:
+        arrays["param." + n] = p
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays) - 4096  # bytes per file, its .npy header left out
+    rng = np.random.default_rng(20240)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        room = max(share // a.itemsize, 1)
+        if a.size > room:
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=room, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 _JSON_OUT = None  # the process's original stdout: the one JSON line goes there
+
 
 
 def emit(obj) -> None:
@@ -1072,11 +1118,18 @@ def main():
 
     fused_ce = wl["loss"] == "CE" and hasattr(run, "forward_loss") and not wl.get("compile")
 
+    last: dict = {}  # the step's returned tensors (--dump-outputs); a replay rewrites them in place
+
     def fwd_bwd():
         if fused_ce:  # model + criterion as one node (GCN.forward_loss = training_step's pair)
-            run.forward_loss(b.x, b.edge_index, b.batch, b.y, None, B)[1].backward(one)
+            logits, loss = run.forward_loss(b.x, b.edge_index, b.batch, b.y, None, B)
         else:
-            loss_fn(wl, run(b.x, b.edge_index, b.batch, B), b.y).backward(one)
+            logits = run(b.x, b.edge_index, b.batch, B)
+            loss = loss_fn(wl, logits, b.y)
+        if args.dump_outputs:
+            last["logits"], last["loss"] = logits.detach(), loss.detach()
+        del logits
+        loss.backward(one)
 
     # GIN under SyncBN all-reduces inside its forward and backward (RCCL collectives)
     plan = step_plan(2 if multi else 1, bool(args.graph), sync_bn,
@@ -1102,6 +1155,8 @@ def main():
         elapsed = t.item()
     ms_per_step = elapsed / args.steps * 1e3
     value = B * world * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:  # before anything below steps the model again
+        dump_outputs(args.dump_outputs, last, model)
 
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "graphs/s", "n_gpus": world,
@@ -1121,12 +1176,13 @@ def main():
     }
     if plan_info.get("segments"):
         out["config"]["step_segments"] = plan_info["segments"]
+    kernel_timing = args.full and not args.no_kernel_timing  # runs of their own: --full only
     bpb = step_bytes(b, wl)
     out["step_hbm_roofline"] = {
         "bytes_per_graph": round(bpb / B, 1),
         "achieved_GBps_per_gpu": round(value / world * bpb / B / 1e9, 1),
         "frac_of_8TBps": round(value / world * bpb / B / (HBM_PEAK_GBS * 1e9), 4)}
-    if rank == 0 and not args.no_kernel_timing and args.workload == "c2":
+    if rank == 0 and kernel_timing and args.workload == "c2":
         rows = []
         for kt in time_dominant_kernels(model, b, dev):
             achieved = kt["flops"] / (kt["ms"] * 1e-3) / 1e12
@@ -1145,7 +1201,7 @@ def main():
         rows.sort(key=lambda r: -r["avg_launch_ms"])
         out["roofline"] = rows[0]  # the dominant kernel (longest launch)
         out["roofline_next"] = rows[1:]
-    if rank == 0 and not args.no_kernel_timing and wl["model"] == "gat":
+    if rank == 0 and kernel_timing and wl["model"] == "gat":
         rows = []
         for kt in time_gat_in_proj(model, b, dev, wl):
             sec = kt["ms"] * 1e-3
@@ -1170,7 +1226,7 @@ def main():
         out["roofline_next"] = rows[1:]
     # one rank only: the eager step's gradient all-reduce (and GIN's SyncBN) would wait on ranks
     # that have left for destroy_process_group
-    if rank == 0 and world == 1 and args.entries and not args.no_kernel_timing:
+    if rank == 0 and world == 1 and args.entries and kernel_timing:
         kind = {"gcn": "gcn", "gin": "gin", "gat": "gat"}[wl["model"]]
         rows, tot = profile_entries(eager_step_fn(fwd_bwd, bucket, opt), dev,
                                     GraphStats(b, kind))
@@ -1178,9 +1234,9 @@ def main():
         out["entries_total"] = tot
         if args.workload in ("c4", "c5k4", "c5k16") or "roofline" not in out:
             out["roofline"], out["roofline_next"] = layer_roofline(rows, args.workload)
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and kernel_timing:
         out["knn_graph"] = time_knn(b, wl, dev)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(wl, B, args.cpu_seconds, c1=args.workload == "c2")
     if rank == 0:
         emit(out)

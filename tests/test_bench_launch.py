@@ -50,6 +50,47 @@ def test_world_size_mismatch_refused():
     assert "WORLD_SIZE=2" in (p.stderr + p.stdout)
 
 
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: logits, loss, one grad.<name> and one param.<name> per parameter, all
+    float32; an array above its share of the byte budget is cut to the same seeded sample on
+    every call, and the files together stay under the budget."""
+    import numpy as np
+    import torch
+
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+
+    torch.manual_seed(0)
+    model = torch.nn.Linear(64, 32)
+    logits = model(torch.randn(16, 64))
+    loss = logits.square().mean()
+    loss.backward()
+    last = {"logits": logits.detach(), "loss": loss.detach()}
+    names = {"logits", "loss", "grad.weight", "grad.bias", "param.weight", "param.bias"}
+
+    bench.dump_outputs(str(tmp_path / "a"), last, model)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == names and all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["logits"], logits.detach().numpy())
+    assert np.array_equal(got["grad.weight"], model.weight.grad.numpy())
+    assert np.array_equal(got["param.weight"], model.weight.detach().numpy())
+    assert got["loss"].shape == () and got["loss"] == np.float32(loss.item())
+
+    budget = 6 * (4096 + 4 * 100)  # 100 elements per file: weight (2048) and logits (512) are cut
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), last, model)
+    cut = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert set(cut) == names
+    assert cut["param.weight"].shape == (100,) and cut["logits"].shape == (100,)
+    assert np.array_equal(cut["param.bias"], got["param.bias"])  # small arrays stay whole
+    assert set(cut["param.weight"].tolist()) <= set(got["param.weight"].reshape(-1).tolist())
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= budget
+
+
 def test_pmc_traffic_prefers_the_workloads_own_pass():
     """bench.pmc_traffic: a "<workload>:<kernel>" key (the PMC pass recorded for that workload)
     wins over the bare kernel name, which stays the fallback; unknown kernels give (None, None).

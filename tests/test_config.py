@@ -2,6 +2,9 @@
 configs/config.py:59-65, utils/placeholder.py): the experiment's model section builds against
 this package's classes unchanged (field names incl. the `hiddden_channels` typo), Placeholder
 semantics, isinstance dispatch, and state_dict keys identical to the PyG-named oracle modules."""
+import json
+import os
+
 import pytest
 import torch
 
@@ -86,7 +89,59 @@ def test_gat_settransformer_readout_out_of_scope():
         GAT(8, [8, 8], 2, heads=2, dropout=0.0, num_st_seed_points=4)
 
 
-REFERENCE_CONFIG = "/root/reference/configs/config.py"
+# the reference experiment's settings (configs/config.py), recorded as data
+REFERENCE_SETTINGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                  "reference_experiment.json")
+
+REFERENCE_EXPERIMENT = '''
+import json
+
+from lesion_gnn.datasets.aptos import AptosConfig
+from lesion_gnn.datasets.datamodule import DataConfig
+from lesion_gnn.datasets.ddr import DDRConfig, DDRVariant
+from lesion_gnn.datasets.nodes.lesions import LesionsNodesConfig, TimmEncoderFeatures
+from lesion_gnn.models.base import LossType, OptimizerAlgo, OptimizerConfig
+from lesion_gnn.models.gat import GATConfig
+from lesion_gnn.transforms import TransformConfig
+from lesion_gnn.utils import ClassWeights
+from lesion_gnn.utils.config import Config
+
+__all__ = ["cfg"]
+
+S = json.load(open({settings!r}))
+NODES = LesionsNodesConfig(
+    feature_source=TimmEncoderFeatures(timm_model=S["nodes"]["timm_model"],
+                                       layer=S["nodes"]["layer"]),
+    reinterpolation=tuple(S["nodes"]["reinterpolation"]))
+
+
+def dataset(d):
+    if d["dataset"] == "DDR":
+        return DDRConfig(root=d["root"], nodes=NODES, variant=DDRVariant[d["variant"]])
+    return AptosConfig(root=d["root"], nodes=NODES)
+
+
+O, M = S["optimizer"], S["model"]
+assert M["name"] == "GAT"
+cfg = Config(
+    dataset=DataConfig(
+        train_datasets=[dataset(d) for d in S["train_datasets"]],
+        val_datasets=[dataset(d) for d in S["val_datasets"]],
+        test_datasets=[dataset(d) for d in S["test_datasets"]],
+        transforms=[TransformConfig(name=t["name"], kwargs=t["kwargs"])
+                    for t in S["transforms"]],
+        batch_size=S["batch_size"], num_workers=S["num_workers"]),
+    model=GATConfig(
+        optimizer=OptimizerConfig(lr=O["lr"], lr_scheduler=O["lr_scheduler"],
+                                  weight_decay=O["weight_decay"], algo=OptimizerAlgo[O["algo"]],
+                                  loss_type=LossType[O["loss_type"]],
+                                  class_weights_mode=ClassWeights[O["class_weights_mode"]]),
+        hiddden_channels=M["hiddden_channels"], heads=M["heads"], dropout=M["dropout"],
+        compile=M["compile"]),
+    monitored_metric=S["monitored_metric"], monitor_mode=S["monitor_mode"],
+    early_stopping_patience=S["early_stopping_patience"], max_epochs=S["max_epochs"],
+    seed=S["seed"], project_name=S["project_name"], tags=S["tags"])
+'''
 
 EXPERIMENT = '''
 from lesion_gnn.datasets.aptos import AptosConfig
@@ -147,18 +202,37 @@ def test_experiment_file_with_reference_imports(tmp_path):
     assert repr(t.transforms[-1]) == "ToSparseTensor()"  # compile=False (datamodule.py:44-45)
 
 
-@pytest.mark.skipif(not __import__("os").path.exists(REFERENCE_CONFIG),
-                    reason="reference checkout not mounted (GPU box)")
-def test_reference_config_file_loads_unchanged():
-    """The reference's own experiment file, read in place (not copied), builds against this
-    package: GAT with hiddden_channels=[128]*4, heads 2, MSE (configs/config.py:56-65)."""
+def test_reference_config_file_loads_unchanged(tmp_path):
+    """The reference experiment (configs/config.py) builds against this package: an experiment
+    file written against the reference's module paths and field names (GATConfig from
+    lesion_gnn.models.gat, `hiddden_channels`, `reinterpolation`, `early_stopping_patience`),
+    every value taken from the settings recorded in golden/reference_experiment.json, loads
+    through get_config: GAT with hiddden_channels=[128]*4, heads 2, MSE (configs/config.py:56-65)."""
+    from lesion_gnn_amd.datasets.ddr import DDRVariant
     from lesion_gnn_amd.utils.config import Config, get_config
 
-    cfg = get_config(REFERENCE_CONFIG)
+    want = json.load(open(REFERENCE_SETTINGS))
+    f = tmp_path / "reference_experiment.py"
+    f.write_text(REFERENCE_EXPERIMENT.format(settings=REFERENCE_SETTINGS))
+    cfg = get_config(f)
     assert isinstance(cfg, Config) and isinstance(cfg.model, GATConfig)
     assert cfg.model.hiddden_channels == [128] * 4 and cfg.model.heads == 2
     assert cfg.model.compile is True and cfg.dataset.batch_size == 10000
     assert cfg.dataset.transforms[0].name == "KNNGraph"
+    assert cfg.dataset.transforms[0].kwargs == {"k": 6, "loop": True}
+    assert cfg.model.dropout == 0.35 and cfg.model.optimizer.loss_type is LossType.MSE
+    assert cfg.model.optimizer.algo is OptimizerAlgo.ADAM
+    assert cfg.model.optimizer.lr == 1e-3 and cfg.model.optimizer.weight_decay == 2e-6
+    assert cfg.model.optimizer.class_weights_mode is ClassWeights.UNIFORM
+    assert [d.name for d in cfg.dataset.test_datasets] == ["DDR", "Aptos"]
+    assert cfg.dataset.train_datasets[0].variant is DDRVariant.TRAIN
+    assert cfg.dataset.val_datasets[0].variant is DDRVariant.VALID
+    assert cfg.dataset.train_datasets[0].nodes.reinterpolation == (512, 512)
+    assert cfg.dataset.train_datasets[0].nodes.feature_source.timm_model == \
+        want["nodes"]["timm_model"]
+    assert (cfg.max_epochs, cfg.seed, cfg.early_stopping_patience) == (500, 1234, None)
+    assert (cfg.monitored_metric, cfg.monitor_mode) == ("val_DDR_kappa", "max")
+    assert cfg.project_name == "SweepLesionsGNN" and cfg.tags == ["LESIONS"]
     m = _fill_and_build(cfg)
     assert isinstance(m, GATModule) and m.is_regression
     want = ref.GAT(1025, [128] * 4, 1, heads=2, dropout=0.35).state_dict()

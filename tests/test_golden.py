@@ -40,9 +40,18 @@ def test_inputs_regenerate(name):
     assert np.array_equal(g["y"], b.y.numpy())
 
 
-@pytest.mark.parametrize("name", list(mg.CASES))
-def test_oracle_reproduces_golden(name):
+@pytest.fixture
+def one_thread():
+    """One intra-op thread (as make_golden.py ran), put back afterwards: the tests that follow in
+    the same process compare against the oracle at the thread count they were started with."""
+    n = torch.get_num_threads()
     torch.set_num_threads(1)
+    yield
+    torch.set_num_threads(n)
+
+
+@pytest.mark.parametrize("name", list(mg.CASES))
+def test_oracle_reproduces_golden(name, one_thread):
     g = load(name)
     kind, mkw, bkw, loss_kind, seed = mg.CASES[name]
     m = mg.MODELS[kind](**mkw)

@@ -14,7 +14,7 @@ if [ -n "${TESTS:-}" ]; then
   case $rc in 0|1) ;; *) echo "pytest rc=$rc"; exit $rc;; esac
 fi
 for w in ${BENCH:-}; do
-  timeout -k 10 300 python bench.py --workload $w --steps ${STEPS:-200} --warmup 30 --cpu-seconds 0 \
+  timeout -k 10 300 python bench.py --full --workload $w --steps ${STEPS:-200} --warmup 30 --cpu-seconds 0 \
     > "$OUT/bench_$w.json" 2> "$OUT/bench_$w.err" || { tail -20 "$OUT/bench_$w.err"; exit 1; }
   python -c "
 import json; d=json.load(open('$OUT/bench_$w.json')); r=d.get('roofline') or {}
