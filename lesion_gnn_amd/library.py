@@ -5,9 +5,12 @@ it (src/lesion_gnn/models/gin.py:56, gat.py:84, drgnet.py:103; configs/config.py
 compile=True for the GAT run). Under Dynamo every op of this package dispatches here instead of
 to its eager `torch.autograd.Function` (ops.py): each HIP op is a `torch.library.custom_op` in
 namespace `lgnn` with
-  * a real (CUDA-key, i.e. HIP) implementation that runs the same eager code — the same kernels
-    through the same C ABI — on a stub autograd context,
+  * a real (CUDA-key, i.e. HIP) implementation that calls the op's plain forward / backward
+    function of ops.py (`<op>_fwd` / `<op>_bwd`), the one the eager autograd.Function calls, and
+    returns fields of its saved record by name; the `_bwd` ops rebuild that record from their
+    named arguments and the op's plan function,
   * a fake (meta) implementation giving output shapes from symbolic input shapes (dynamic=True),
+    path-dependent ones from the same plan function,
   * `register_autograd` wiring its backward to a second custom op (`lgnn::<op>_bwd`).
 The graph structure is built by `lgnn::graph_build` / `lgnn::batch_ptr` / `lgnn::weighted_csr`,
 so a compiled model's FX graph holds only `lgnn` ops: no graph break, and nothing for Inductor to
@@ -26,7 +29,7 @@ import torch
 from torch import Tensor
 from torch.library import custom_op
 
-from . import _lib
+from . import _lib, ops
 from .graph import Csr
 
 GPARTS = ("rowptr", "col", "w", "tptr", "tidx", "tw", "tmap", "tile_open", "err", "batch", "gptr")
@@ -46,21 +49,6 @@ def _opt(t: Tensor) -> Tensor | None:
 
 def _enc(t: Tensor | None, dev) -> Tensor:
     return _none(dev) if t is None else t
-
-
-class _Ctx:
-    """Stand-in for an autograd ctx: lets a custom op's real implementation run the eager
-    autograd.Function's forward / backward body unchanged."""
-
-    def __init__(self, needs_input_grad=()):
-        self.saved_tensors = ()
-        self.needs_input_grad = tuple(needs_input_grad)
-
-    def save_for_backward(self, *ts):
-        self.saved_tensors = ts
-
-    def mark_non_differentiable(self, *ts):
-        pass
 
 
 class TGraph:
@@ -207,10 +195,7 @@ def _grad_list(ts, dev) -> list[Tensor]:
 @custom_op("lgnn::node_linear", mutates_args=(), device_types="cuda")
 def node_linear(x: Tensor, W: Tensor, b: Optional[Tensor], g: list[Tensor], kind: str,
                 self_scale: float, act: int) -> Tensor:
-    from .ops import _NodeLinear
-
-    graph = TGraph(g, kind) if kind else None
-    return _NodeLinear.forward(_Ctx(), x, W, b, graph, kind, self_scale, act)
+    return ops.node_linear_fwd(x, W, b, TGraph(g, kind) if kind else None, kind, self_scale, act)[0]
 
 
 @node_linear.register_fake
@@ -221,14 +206,10 @@ def _(x, W, b, g, kind, self_scale, act):
 @custom_op("lgnn::node_linear_bwd", mutates_args=(), device_types="cuda")
 def node_linear_bwd(dy: Tensor, x: Tensor, W: Tensor, y: Tensor, has_b: bool, g: list[Tensor],
                     kind: str, self_scale: float, act: int, want_dx: bool) -> list[Tensor]:
-    from .ops import _NodeLinear
-
-    ctx = _Ctx((want_dx,))
-    ctx.save_for_backward(x.contiguous(), W.contiguous(), y)
-    ctx.graph = TGraph(g, kind) if kind else None
-    ctx.kind, ctx.self_scale, ctx.act, ctx.has_b = kind, self_scale, act, has_b
-    dx, dW, db = _NodeLinear.backward(ctx, dy)[:3]
-    return _grad_list([dx, dW, db], x.device)
+    sv = ops.LinearSaved(x=x.contiguous(), W=W.contiguous(), y=y,
+                         graph=TGraph(g, kind) if kind else None, kind=kind, self_scale=self_scale,
+                         act=act, has_b=has_b)
+    return _grad_list(ops.node_linear_bwd(sv, dy, want_dx), x.device)
 
 
 @node_linear_bwd.register_fake
@@ -257,25 +238,19 @@ node_linear.register_autograd(_node_linear_backward, setup_context=_node_linear_
 @custom_op("lgnn::s3_weight_planes_multi", mutates_args=(), device_types="cuda")
 def s3_weight_planes_multi(Ws: list[Tensor], transposed: list[bool], bf16: bool) -> Tensor:
     """ops.s3_weight_bundle: every split-3 weight operand of a step in one flat buffer."""
-    from .ops import s3_bundle_raw
-
-    return s3_bundle_raw(Ws, transposed, bf16)
+    return ops.s3_bundle_raw(Ws, transposed, bf16)
 
 
 @s3_weight_planes_multi.register_fake
 def _(Ws, transposed, bf16):
-    from .ops import _s3_bundle_sizes
-
-    n = sum(_s3_bundle_sizes([tuple(W.shape) for W in Ws], transposed, bf16))
+    n = sum(ops._s3_bundle_sizes([tuple(W.shape) for W in Ws], transposed, bf16))
     return Ws[0].new_empty(n, dtype=torch.int16)
 
 
 @custom_op("lgnn::dense_linear", mutates_args=(), device_types="cuda")
 def dense_linear(x: Tensor, W: Tensor, b: Optional[Tensor], bf16: bool,
                  wp: Optional[Tensor]) -> Tensor:
-    from .ops import _DenseLinear
-
-    return _DenseLinear.forward(_Ctx(), x, W, b, bf16, wp)
+    return ops.dense_linear_fwd(x, W, b, bf16, wp)[0]
 
 
 @dense_linear.register_fake
@@ -286,15 +261,11 @@ def _(x, W, b, bf16, wp=None):
 @custom_op("lgnn::dense_linear_bwd", mutates_args=(), device_types="cuda")
 def dense_linear_bwd(dy: Tensor, x: Tensor, W: Tensor, has_b: bool, bf16: bool,
                      want_dx: bool) -> list[Tensor]:
-    from .ops import _DenseLinear, bf16_mfma_fits
-
-    ctx = _Ctx((want_dx,))
+    plan = ops.dense_plan(W.shape[0], bf16)
     # the MFMA kernels round an fp32 x themselves (as the eager path hands it over)
-    xs = x.to(torch.bfloat16) if bf16 and not bf16_mfma_fits(W.shape[0]) else x.contiguous()
-    ctx.save_for_backward(xs, W.contiguous())
-    ctx.bf16, ctx.has_b = bf16, has_b
-    dx, dW, db = _DenseLinear.backward(ctx, dy)[:3]
-    return _grad_list([dx, dW, db], x.device)
+    sv = ops.DenseSaved(x=x.to(torch.bfloat16) if plan.x_bf16 else x.contiguous(), W=W.contiguous(),
+                        wt=None, bf16=bf16, has_b=has_b, plan=plan)
+    return _grad_list(ops.dense_linear_bwd(sv, dy, want_dx), x.device)
 
 
 @dense_linear_bwd.register_fake
@@ -322,12 +293,10 @@ dense_linear.register_autograd(_dense_backward, setup_context=_dense_setup)
 @custom_op("lgnn::spmm", mutates_args=(), device_types="cuda")
 def spmm(x: Tensor, g: list[Tensor], self_scale: float, transpose: bool) -> Tensor:
     """Y = A X (+ self_scale X) over the bundle's target CSR, or over its transpose."""
-    from .ops import _f32c, spmm_raw
-
     c = TGraph(g).csr("")
     if transpose:
-        return spmm_raw(c.tptr, c.tidx, c.tw, self_scale, _f32c(x))
-    return spmm_raw(c.rowptr, c.col, c.w, self_scale, _f32c(x))
+        return ops.spmm_raw(c.tptr, c.tidx, c.tw, self_scale, ops._f32c(x))
+    return ops.spmm_raw(c.rowptr, c.col, c.w, self_scale, ops._f32c(x))
 
 
 @spmm.register_fake
@@ -358,9 +327,8 @@ spmm.register_autograd(_spmm_backward, setup_context=_spmm_setup)
 @custom_op("lgnn::pool_head", mutates_args=(), device_types="cuda")
 def pool_head(x: Tensor, Wout: Tensor, bout: Tensor, g: list[Tensor],
               mean: bool) -> list[Tensor]:
-    from .ops import _f32c, pool_head_fwd
-
-    pooled, logits = pool_head_fwd(_f32c(x), TGraph(g), mean, _f32c(Wout), _f32c(bout))
+    pooled, logits = ops.pool_head_fwd(ops._f32c(x), TGraph(g), mean, ops._f32c(Wout),
+                                       ops._f32c(bout))
     return [logits, pooled]
 
 
@@ -373,10 +341,8 @@ def _(x, Wout, bout, g, mean):
 @custom_op("lgnn::pool_head_bwd", mutates_args=(), device_types="cuda")
 def pool_head_bwd(dlogits: Tensor, pooled: Tensor, Wout: Tensor, g: list[Tensor], mean: bool,
                   num_nodes: int, want_dx: bool) -> list[Tensor]:
-    from .ops import _f32c, pool_bwd, pool_head_bwd as phb
-
-    dp, dWo, dbo = phb(_f32c(dlogits), pooled, Wout)
-    dx = pool_bwd(dp, TGraph(g), mean, num_nodes) if want_dx else None
+    dp, dWo, dbo = ops.pool_head_bwd(ops._f32c(dlogits), pooled, Wout)
+    dx = ops.pool_bwd(dp, TGraph(g), mean, num_nodes) if want_dx else None
     return _grad_list([dx, dWo, dbo], pooled.device)
 
 
@@ -405,9 +371,7 @@ pool_head.register_autograd(_pool_head_backward, setup_context=_pool_head_setup)
 
 @custom_op("lgnn::segment_pool", mutates_args=(), device_types="cuda")
 def segment_pool(x: Tensor, g: list[Tensor], mean: bool) -> Tensor:
-    from .ops import _f32c, pool_head_fwd
-
-    return pool_head_fwd(_f32c(x), TGraph(g), mean)[0]
+    return ops.pool_head_fwd(ops._f32c(x), TGraph(g), mean)[0]
 
 
 @segment_pool.register_fake
@@ -417,9 +381,7 @@ def _(x, g, mean):
 
 @custom_op("lgnn::segment_pool_bwd", mutates_args=(), device_types="cuda")
 def segment_pool_bwd(dp: Tensor, g: list[Tensor], mean: bool, num_nodes: int) -> Tensor:
-    from .ops import _f32c, pool_bwd
-
-    return pool_bwd(_f32c(dp), TGraph(g), mean, num_nodes)
+    return ops.pool_bwd(ops._f32c(dp), TGraph(g), mean, num_nodes)
 
 
 @segment_pool_bwd.register_fake
@@ -501,13 +463,9 @@ def gat_conv(x: Tensor, W: Tensor, att_src: Tensor, att_dst: Tensor, bias: Optio
              g: list[Tensor], heads: int, slope: float, mask: Optional[Tensor], act: int,
              bf16: bool, wp: Optional[Tensor], wpt: Optional[Tensor]) -> list[Tensor]:
     """[Y, XP, a_s, a_d, alpha] (the eager _GATConv forward and what it saves)."""
-    from .ops import _GATConv
-
-    ctx = _Ctx()
-    Y = _GATConv.forward(ctx, x, W, att_src, att_dst, bias, TGraph(g, "gat"), heads, slope, mask,
-                         act, bf16, wp)
-    _x, _W, _as, _ad, XP, a_s, a_d, alpha, _Y, _m = ctx.saved_tensors
-    return [Y, XP, a_s, a_d, alpha]
+    Y, sv = ops.gat_conv_fwd(x, W, att_src, att_dst, bias, TGraph(g, "gat"), heads, slope, mask,
+                             act, bf16, wp)
+    return [Y, sv.XP, sv.a_s, sv.a_d, sv.alpha]
 
 
 @gat_conv.register_fake
@@ -524,22 +482,22 @@ def gat_conv_bwd(dY: Tensor, x: Tensor, W: Tensor, att_src: Tensor, att_dst: Ten
                  mask: Optional[Tensor], g: list[Tensor], heads: int, slope: float, act: int,
                  bf16: bool, has_bias: bool, want_dx: bool,
                  wpt: Optional[Tensor]) -> list[Tensor]:
-    from .ops import GAT_S3, _GATConv, fast_shape
-
-    HC = W.shape[0]
-    ctx = _Ctx((want_dx,))
-    ctx.wpt = wpt
-    ctx.save_for_backward(x.contiguous(), W.contiguous(), att_src.reshape(-1),
-                          att_dst.reshape(-1), XP, a_s, a_d, alpha, Y, mask)
-    ctx.graph, ctx.heads, ctx.slope, ctx.act = TGraph(g, "gat"), heads, slope, act
-    ctx.bf16, ctx.dense = bf16, bf16 or not fast_shape(W.shape[1], HC) or GAT_S3
-    ctx.has_bias = has_bias
-    ctx.att_shape = tuple(att_src.shape)
-    dx, dW = _GATConv.backward(ctx, dY)[:2]
+    sv = _gat_saved(x, W, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, g, heads, slope, act,
+                    bf16, has_bias, wpt)
     # the attention / bias gradients are ONE reduction buffer [att_src | att_dst | bias]
     # (outputs of a custom op may not alias each other): returned whole and split into views by
     # the autograd formula below, instead of three copies
-    return _grad_list([dx, dW, ctx.red], x.device)
+    return _grad_list(ops.gat_conv_bwd(sv, dY, want_dx), x.device)
+
+
+def _gat_saved(x, W, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, g, heads, slope, act, bf16,
+               has_bias, wpt):
+    """ops.GatSaved from the named arguments of a GAT backward op."""
+    return ops.GatSaved(x=x.contiguous(), W=W.contiguous(), att_src=att_src.reshape(-1),
+                        att_dst=att_dst.reshape(-1), XP=XP, a_s=a_s, a_d=a_d, alpha=alpha, Y=Y,
+                        mask=mask, wt=None, wpt=wpt, graph=TGraph(g, "gat"), heads=heads,
+                        slope=slope, act=act, bf16=bf16, has_bias=has_bias,
+                        plan=ops.gat_plan(W.shape[1], W.shape[0], bf16))
 
 
 @gat_conv_bwd.register_fake
@@ -582,13 +540,10 @@ def gat_conv_head(x: Tensor, W: Tensor, att_src: Tensor, att_dst: Tensor, bias: 
                   wp: Optional[Tensor], wpt: Optional[Tensor]) -> list[Tensor]:
     """The GAT model's last conv + global pool + out_proj as one node (ops._GATConvHead):
     [logits, Y, XP, a_s, a_d, alpha, pooled]."""
-    from .ops import _GATConvHead
-
-    ctx = _Ctx()
-    logits = _GATConvHead.forward(ctx, x, W, att_src, att_dst, bias, W_out, b_out,
-                                  TGraph(g, "gat"), heads, slope, mask, act, bf16, mean, wp)
-    s = ctx.saved_tensors  # x, W, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, pooled, W_out
-    return [logits, s[8], s[4], s[5], s[6], s[7], s[10]]
+    logits, sv = ops.gat_head_fwd(x, W, att_src, att_dst, bias, W_out, b_out, TGraph(g, "gat"),
+                                  heads, slope, mask, act, bf16, mean, wp)
+    c = sv.conv
+    return [logits, c.Y, c.XP, c.a_s, c.a_d, c.alpha, sv.pooled]
 
 
 @gat_conv_head.register_fake
@@ -610,22 +565,10 @@ def gat_conv_head_bwd(dlogits: Tensor, x: Tensor, W: Tensor, att_src: Tensor, at
                       want_dx: bool, wpt: Optional[Tensor]) -> list[Tensor]:
     """[dx, dW, red (= [datt_src | datt_dst | dbias]), dW_out, db_out]: the readout's backward
     formed inside the edge kernel's load (lgnn_gat_bwd_edge_pool), no dH tensor."""
-    from .ops import GAT_S3, _GATConvHead, _SubCtx, fast_shape
-
-    HC = W.shape[0]
-    sub = _SubCtx(want_dx)
-    sub.graph, sub.heads, sub.slope, sub.act = TGraph(g, "gat"), heads, slope, act
-    sub.bf16, sub.dense = bf16, bf16 or not fast_shape(W.shape[1], HC) or GAT_S3
-    sub.has_bias = has_bias
-    sub.att_shape = tuple(att_src.shape)
-    sub.wt = None
-    sub.wpt = wpt
-    ctx = _Ctx((want_dx,))
-    ctx.save_for_backward(x.contiguous(), W.contiguous(), att_src.reshape(-1),
-                          att_dst.reshape(-1), XP, a_s, a_d, alpha, Y, mask, pooled, W_out)
-    ctx.sub, ctx.head_graph, ctx.head_mean = sub, TGraph(g, "gat"), mean
-    grads = _GATConvHead.backward(ctx, dlogits)
-    return _grad_list([grads[0], grads[1], sub.red, grads[5], grads[6]], x.device)
+    conv = _gat_saved(x, W, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, g, heads, slope, act,
+                      bf16, has_bias, wpt)
+    sv = ops.HeadSaved(conv, pooled, W_out, mean)
+    return _grad_list(ops.gat_head_bwd(sv, dlogits, want_dx), x.device)
 
 
 @gat_conv_head_bwd.register_fake
@@ -685,16 +628,12 @@ def gin_conv(x: Tensor, W1: Tensor, b1: Tensor, gamma: Optional[Tensor], beta: O
     forward). Functional: in training the BatchNorm running statistics are NOT updated here —
     lgnn::bn_running_update does it from the returned batch sums (a mutating op cannot carry an
     autograd formula); in eval the running statistics are read."""
-    from .ops import _GINConv
-
-    ctx = _Ctx()
     rm, rv = (None, None) if training else (running_mean, running_var)
     bn = _bn_stub(gamma, beta, rm, rv, None, bn_eps, 0.1)
-    H = _GINConv.forward(ctx, x, W1, b1, gamma, beta, W2, b2, TGraph(g, "gin"), bn, training,
-                         eps, mask, act, None, None)
-    S, Z1, A1, _H, _W1, _W2, mean, invstd, scale, shift, _m = ctx.saved_tensors
-    return [H, _none(x.device) if ctx.gathered else S, Z1, A1, mean, invstd, scale, shift,
-            _enc(ctx.bn_sums, x.device)]
+    H, sums, sv = ops.gin_conv_fwd(x, W1, b1, W2, b2, TGraph(g, "gin"), bn, training, eps, mask,
+                                   act)
+    return [H, _none(x.device) if sv.plan.gathered else sv.S, sv.Z1, sv.A1, sv.mean, sv.invstd,
+            sv.scale, sv.shift, _enc(sums, x.device)]
 
 
 @custom_op("lgnn::bn_running_update", mutates_args=("running_mean", "running_var", "nbt"),
@@ -703,10 +642,8 @@ def bn_running_update(running_mean: Tensor, running_var: Tensor, nbt: Optional[T
                       sums: Tensor, count: int, bn_eps: float, momentum: float) -> None:
     """BatchNorm1d running statistics from a batch's (sum z, sum z^2) (lgnn_bn_finalize in
     training mode), torch semantics (unbiased variance; momentum < 0: cumulative average)."""
-    from .ops import bn_finalize
-
     bn = _bn_stub(None, None, running_mean, running_var, nbt, bn_eps, momentum)
-    bn_finalize(sums, float(count), bn, True, running_mean.numel(), running_mean.device)
+    ops.bn_finalize(sums, float(count), bn, True, running_mean.numel(), running_mean.device)
 
 
 @bn_running_update.register_fake
@@ -717,11 +654,8 @@ def _(running_mean, running_var, nbt, sums, count, bn_eps, momentum):
 @gin_conv.register_fake
 def _(x, W1, b1, gamma, beta, W2, b2, running_mean, running_var, g, training, eps, bn_eps,
       mask, act):
-    from .ops import fast_shape, wide_shape
-
     M, N1 = x.shape[0], W1.shape[0]
-    # the eager rule (_GINConv.forward): S is saved for the tile fast path and the wide path
-    gathered = not (fast_shape(W1.shape[1], N1) or wide_shape(W1.shape[1], N1))
+    gathered = ops.gin_plan(W1.shape[1], N1, W2.shape[0]).gathered
     S = _none(x.device) if gathered else torch.empty_like(x)
     sums = x.new_empty(2 * N1, dtype=torch.float64) if training else _none(x.device)
     return [x.new_empty(M, W2.shape[0]), S, x.new_empty(M, N1), x.new_empty(M, N1)] + \
@@ -734,17 +668,13 @@ def gin_conv_bwd(dH: Tensor, S: Tensor, Z1: Tensor, A1: Tensor, H: Tensor, W1: T
                  mask: Optional[Tensor], g: list[Tensor], training: bool, count: int,
                  act: int, affine: bool, gathered: bool, eps: float,
                  want_dx: bool) -> list[Tensor]:
-    from .ops import _GINConv, gin_bn_fused
-
-    ctx = _Ctx((want_dx,))
-    ctx.save_for_backward(S.contiguous(), Z1, A1, H, W1.contiguous(), W2.contiguous(), mean,
-                          invstd, scale, shift, mask)
-    ctx.graph, ctx.self_scale, ctx.gathered = TGraph(g, "gin"), 1.0 + eps, gathered
-    ctx.training, ctx.count, ctx.group, ctx.act = training, float(count), None, act
-    ctx.affine = affine
-    ctx.bn_fused = gin_bn_fused(W1.shape[1], W1.shape[0], W2.shape[0])
-    grads = _GINConv.backward(ctx, dH)[:7]
-    return _grad_list(grads, H.device)
+    plan = ops.gin_plan(W1.shape[1], W1.shape[0], W2.shape[0])
+    assert plan.gathered == gathered, "GIN path switches changed between forward and backward"
+    sv = ops.GinSaved(S=S.contiguous(), Z1=Z1, A1=A1, H=H, W1=W1.contiguous(), W2=W2.contiguous(),
+                      mean=mean, invstd=invstd, scale=scale, shift=shift, mask=mask,
+                      graph=TGraph(g, "gin"), self_scale=1.0 + eps, training=training,
+                      count=float(count), group=None, act=act, affine=affine, plan=plan)
+    return _grad_list(ops.gin_conv_bwd(sv, dH, want_dx), H.device)
 
 
 @gin_conv_bwd.register_fake
@@ -786,48 +716,32 @@ gin_conv.register_autograd(_gin_backward, setup_context=_gin_setup)
 # ----------------------------------------------------------------------------------------------
 
 
-def _gcn_layout(params, L):
-    from .ops import STACK_MAX, fast_shape, wide_shape
-
-    Ws = [params[2 * l] for l in range(L + 1)]
-    fused = L + 1 <= STACK_MAX and all(fast_shape(W.shape[1], W.shape[0]) for W in Ws)
-    # the eager rule (_GCNStack._fwd): S_l is saved for fast-path and wide layers
-    saved_s = [True] * L if fused else [
-        fast_shape(params[2 + 2 * l].shape[1], params[2 + 2 * l].shape[0]) or
-        wide_shape(params[2 + 2 * l].shape[1], params[2 + 2 * l].shape[0]) for l in range(L)]
-    return fused, saved_s
+def _gcn_plan(params, L):
+    return ops.gcn_plan([tuple(params[2 * l].shape) for l in range(L + 1)], L)
 
 
 @custom_op("lgnn::gcn_stack", mutates_args=(), device_types="cuda")
 def gcn_stack(x: Tensor, g: list[Tensor], mean: bool, L: int,
               params: list[Tensor]) -> list[Tensor]:
     """[logits, pooled, H_0..H_L, S_1..S_L, planes_t or none] (the eager _GCNStack forward)."""
-    from .ops import _GCNStack, adjt_in_planes
-
-    ctx = _Ctx()
-    with adjt_in_planes():  # the op's planes output is a fresh buffer (planes + Â^T room)
-        logits = _GCNStack.forward(ctx, x, TGraph(g, "gcn"), mean, L, *params)
-    sv = ctx.saved_tensors
-    hs = list(sv[2:3 + L])
+    # the op's planes output is one fresh buffer: the planes, then the Â^T room
+    logits, sv = ops.gcn_stack_fwd(x, TGraph(g, "gcn"), mean, L, params, want_dx=True,
+                               adjt_after_planes=True)
+    hs = sv.hs
     ss = [s if s.data_ptr() != x.data_ptr() and all(s.data_ptr() != h.data_ptr() for h in hs)
-          else s.clone() for s in sv[3 + L:3 + 2 * L]]
-    return [logits, sv[1]] + hs + ss + [_enc(ctx.planes_t, x.device)]
+          else s.clone() for s in sv.ss]
+    return [logits, sv.pooled] + hs + ss + [_enc(sv.planes_t, x.device)]
 
 
 @gcn_stack.register_fake
 def _(x, g, mean, L, params):
-    from .ops import BWD_S3, MFMA_MODE
-
     B = g[GPARTS.index("gptr")].shape[0] - 1
     M = x.shape[0]
     Ws = [params[2 * l] for l in range(L + 1)]
-    fused, saved_s = _gcn_layout(params, L)
     hs = [x.new_empty(M, W.shape[0]) for W in Ws]
     ss = [x.new_empty(M, Ws[l + 1].shape[1]) for l in range(L)]
-    from .ops import bwd_planes_numel
-
-    planes = (x.new_empty(bwd_planes_numel(L, M), dtype=torch.int16)
-              if fused and MFMA_MODE == "s3" and BWD_S3 and L >= 1 else _none(x.device))
+    planes = (x.new_empty(ops.bwd_planes_numel(L, M), dtype=torch.int16)
+              if _gcn_plan(params, L).keeps_planes else _none(x.device))
     return [x.new_empty(B, params[2 + 2 * L].shape[0]), x.new_empty(B, Ws[-1].shape[0])] + hs + \
         ss + [planes]
 
@@ -842,15 +756,11 @@ def gcn_stack_bwd(dlogits: Tensor, x: Tensor, pooled: Tensor, hs: list[Tensor],
     backward's barrier words and partial-slot skip words (include/lgnn.h LGNN_SLOT_FLAG0) are
     scratch set and consumed inside this one call, and the next graph build zeroes them; the tile
     flags proper, the only part of tile_open other ops read, are left unchanged."""
-    from .ops import _GCNStack
-
-    fused, saved_s = _gcn_layout(params, L)
-    ctx = _Ctx((want_dx,))
-    ctx.save_for_backward(x.contiguous(), pooled, *hs, *ss, *[p.contiguous() for p in params])
-    ctx.fused, ctx.planes_t, ctx.saved_s = fused, _opt(planes_t), saved_s
-    ctx.graph, ctx.mean, ctx.L = TGraph(g, "gcn"), mean, L
-    out = _GCNStack.backward(ctx, dlogits)
-    return _grad_list([out[0]] + list(out[4:]), x.device)
+    sv = ops.GcnSaved(x=x.contiguous(), pooled=pooled, hs=hs, ss=ss,
+                      params=[p.contiguous() for p in params], planes_t=_opt(planes_t), adjt=None,
+                      graph=TGraph(g, "gcn"), mean=mean, L=L, plan=_gcn_plan(params, L))
+    dx, grads = ops.gcn_stack_bwd(sv, dlogits, want_dx)
+    return _grad_list([dx] + grads, x.device)
 
 
 @gcn_stack_bwd.register_fake
@@ -889,12 +799,8 @@ gcn_stack.register_autograd(_gcn_backward, setup_context=_gcn_setup)
 @custom_op("lgnn::sort_pool", mutates_args=(), device_types="cuda")
 def sort_pool(x: Tensor, g: list[Tensor], k: int) -> list[Tensor]:
     """[out, rank, fill]"""
-    from .ops import _SortPool
-
-    ctx = _Ctx()
-    out = _SortPool.forward(ctx, x, TGraph(g), k)
-    _x, rank, fill = ctx.saved_tensors
-    return [out, rank, fill]
+    out, sv = ops.sort_pool_fwd(x, TGraph(g), k)
+    return [out, sv.rank, sv.fill]
 
 
 @sort_pool.register_fake
@@ -907,12 +813,8 @@ def _(x, g, k):
 @custom_op("lgnn::sort_pool_bwd", mutates_args=(), device_types="cuda")
 def sort_pool_bwd(dout: Tensor, x: Tensor, rank: Tensor, fill: Tensor, g: list[Tensor],
                   k: int) -> Tensor:
-    from .ops import _SortPool
-
-    ctx = _Ctx()
-    ctx.save_for_backward(x.contiguous(), rank, fill)
-    ctx.graph, ctx.k = TGraph(g), k
-    return _SortPool.backward(ctx, dout)[0]
+    sv = ops.SortSaved(x=x.contiguous(), rank=rank, fill=fill, graph=TGraph(g), k=k)
+    return ops.sort_pool_bwd(sv, dout)
 
 
 @sort_pool_bwd.register_fake

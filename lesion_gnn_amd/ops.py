@@ -12,8 +12,11 @@ from __future__ import annotations
 
 import ctypes
 import weakref
+from collections import namedtuple
+from typing import NamedTuple
 
 import torch
+from torch.utils import _pytree as pytree
 
 from . import _lib
 from .graph import Csr, Graph
@@ -224,27 +227,13 @@ def weight_planes(Ws: list, d_in: int, transposed: bool = False, extra: int = 0)
 # (lgnn_graph_build_planes), otherwise as its own launch. Nothing is cached across steps, so a
 # captured step replays the split and sees any write to the weights between replays
 # (load_state_dict, EMA, clipping), eager or captured alike.
-_ADJT_IN_PLANES = [0]  # > 0 inside adjt_in_planes()
-
-
-class adjt_in_planes:
-    """Context: stack forwards put the Â^T room after the transposed planes (one buffer) — the
-    compiled lgnn::gcn_stack op returns that buffer as an output of its own."""
-
-    def __enter__(self):
-        _ADJT_IN_PLANES[0] += 1
-
-    def __exit__(self, *exc):
-        _ADJT_IN_PLANES[0] -= 1
-
-
 def adjt_numel(M) -> int:
     """int16 elements of the Â^T planes the split-3 forward hands to the fused backward."""
     return (M + 63) // 64 * (_lib.LGNN_S3_ADJT_TILE_BYTES // 2)
 
 
 def bwd_planes_numel(L: int, M) -> int:
-    """Size of the buffer the fused GCN forward keeps for its backward (ctx.planes_t): the
+    """Size of the buffer the fused GCN forward keeps for its backward (GcnSaved.planes_t): the
     transposed weight planes, plus the Â^T planes when the single-launch split-3 backward runs."""
     return (L + 1) * 3 * 128 * 128 + (adjt_numel(M) if _s3f(L) and ADJT else 0)
 
@@ -267,13 +256,23 @@ def _adjt_ptr(planes_t: torch.Tensor, L: int):
     return planes_t.data_ptr() + 2 * base if planes_t.numel() > base else None
 
 
-def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, keep: dict | None = None,
-              kind: str = "gcn"):
+def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: str = "gcn"):
+    """stack_fwd_planes without the backward's planes: ([H_0..H_L], [S_1..S_L])."""
+    return stack_fwd_planes(x, graph, Ws, bs, kind)[:2]
+
+
+def stack_fwd_planes(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: str = "gcn",
+                     keep_planes: bool = False, adjt_after_planes: bool = False):
     """in_proj + L x ELU(GCNConv) forward, every width <= 128: returns ([H_0..H_L],
-    [S_1..S_L]). Tiles no edge leaves run fused through every layer (lgnn_gcn_stack_fwd); the
-    rest (graphs straddling 64-node tiles) layer by layer (lgnn_node_linear_fwd_tiles), into the
-    same buffers. With graphs aligned to tiles (C2: N = 64) the second group is empty.
-    kind: the graph build ("gcn", or "gcn_lazy" when only the fused backward follows)."""
+    [S_1..S_L], planes_t, adjt_t). Tiles no edge leaves run fused through every layer
+    (lgnn_gcn_stack_fwd); the rest (graphs straddling 64-node tiles) layer by layer
+    (lgnn_node_linear_fwd_tiles), into the same buffers. With graphs aligned to tiles (C2: N = 64)
+    the second group is empty.
+    kind: the graph build ("gcn", or "gcn_lazy" when only the fused backward follows).
+    keep_planes (split-3 only): planes_t = the transposed weight planes for the split-3 backward,
+    adjt_t = the Â^T tiles for its single-launch form (None when ADJT is off or L > 3) — or, with
+    adjt_after_planes, those tiles in room after the planes inside planes_t (one buffer: the
+    compiled lgnn::gcn_stack op returns it as an output of its own) and adjt_t None."""
     M = x.size(0)
     L = len(Ws) - 1
     dev = x.device
@@ -282,24 +281,22 @@ def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, keep: dict | No
         # the transposed planes (the split-3 backward's dH = G W_l operand) come from the same
         # split when the caller keeps them; the split rides the graph build when this forward
         # builds the graph
-        want_adjt = keep is not None and _s3f(L) and ADJT
-        extra = adjt_numel(M) if want_adjt and _ADJT_IN_PLANES[0] else 0
-        planes, planes_t = plane_buffers(Ws, transposed=keep is not None, extra=extra)
+        want_adjt = keep_planes and _s3f(L) and ADJT
+        extra = adjt_numel(M) if want_adjt and adjt_after_planes else 0
+        planes, planes_t = plane_buffers(Ws, transposed=keep_planes, extra=extra)
         job = plane_job(Ws, x.size(1), planes, planes_t)
         csr, split_done = graph.csr_planes(kind, job)
         if not split_done:
             run_plane_job(job, dev)
-        if extra:  # the Â^T tiles in the room after the planes (the compiled op's one output)
+        if extra:  # the Â^T tiles in the room after the planes
             adjt_t, adjt = None, _adjt_ptr(planes_t, L)
         else:
             adjt_t = torch.empty(adjt_numel(M), dtype=torch.int16, device=dev) \
                 if want_adjt else None
             adjt = _lib.ptr(adjt_t)
-        if keep is not None:
-            keep["planes_t"] = planes_t
-            keep["adjt"] = adjt_t
     else:
         csr = graph.csr(kind)
+        planes_t = adjt_t = None
     open_ = graph.tile_open(kind)
     hs = [torch.empty(M, W.size(0), dtype=torch.float32, device=dev) for W in Ws]
     ss = [torch.empty(M, Ws[l].size(1), dtype=torch.float32, device=dev) for l in range(1, L + 1)]
@@ -315,7 +312,7 @@ def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, keep: dict | No
                       _lib.ptr(planes), Wp, bp, widths, Hp,
                       (ctypes.c_void_p * L)(*[t.data_ptr() for t in ss]), _lib.ptr(open_),
                       adjt, _s(dev))
-            return hs, ss
+            return hs, ss, planes_t, adjt_t
         _lib.call("lgnn_gcn_stack_fwd_s3", _lib.ptr(x), M, x.size(1), 1, _lib.ptr(csr.rowptr),
                   _lib.ptr(csr.col), _lib.ptr(csr.w), L, _lib.ptr(planes), bp, widths, Hp,
                   _lib.ptr(open_), adjt, _s(dev))
@@ -332,7 +329,7 @@ def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, keep: dict | No
                   _lib.ptr(c.w) if c else None, 0.0, _lib.ptr(Ws[l]), _lib.ptr(bs[l]),
                   Ws[l].size(0), _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE,
                   _lib.ptr(hs[l]), _lib.ptr(s_out), _lib.ptr(open_), 1, _s(dev))
-    return hs, ss
+    return hs, ss, planes_t, adjt_t
 
 
 def head_in_stack_bwd(graph: Graph, L: int, C: int, s3: bool) -> bool:
@@ -587,32 +584,65 @@ def pool_bwd(dpooled: torch.Tensor, graph: Graph, mean: bool, M: int) -> torch.T
 # ----------------------------------------------------------------------------------------------
 
 
+# Every op with a compiled twin (library.py) is three plain pieces, shared by its eager
+# autograd.Function and its torch.library custom ops:
+#   <op>_plan(shapes, flags) -> a record of the path decisions (module switches read at call time)
+#   <op>_fwd(inputs...)      -> (outputs..., saved): saved is a record of what the backward needs
+#   <op>_bwd(saved, grad, want_dx, ...) -> every gradient and buffer its callers use
+# The autograd.Functions below only move `saved` through an autograd ctx (_save / _load).
+
+
+def _save(ctx, saved) -> None:
+    """A saved record onto an autograd ctx: its tensors (at any depth) through
+    save_for_backward, the rest of its leaves and its structure as attributes."""
+    leaves, ctx.spec = pytree.tree_flatten(saved)
+    ctx.slots = [i for i, v in enumerate(leaves) if isinstance(v, torch.Tensor)]
+    ctx.save_for_backward(*[leaves[i] for i in ctx.slots])
+    ctx.leaves = [None if isinstance(v, torch.Tensor) else v for v in leaves]
+
+
+def _load(ctx):
+    leaves = list(ctx.leaves)
+    for i, t in zip(ctx.slots, ctx.saved_tensors):
+        leaves[i] = t
+    return pytree.tree_unflatten(leaves, ctx.spec)
+
+
+# graph: a Graph, or None (no aggregation)
+LinearSaved = namedtuple("LinearSaved", "x W y graph kind self_scale act has_b")
+
+
+def node_linear_fwd(x, W, b, graph, kind, self_scale, act):
+    _lib.require_gpu(x, W)
+    x, W = _f32c(x), _f32c(W)
+    b = _f32c(b) if b is not None else None
+    csr = graph.csr(kind) if graph is not None else None
+    y = linear_fwd(x, W, b, act, csr, self_scale)
+    return y, LinearSaved(x, W, y, graph, kind, self_scale, act, b is not None)
+
+
+def node_linear_bwd(sv: LinearSaved, dy, want_dx: bool):
+    """(dx or None, dW, db or None)"""
+    csr = sv.graph.csr(sv.kind) if sv.graph is not None else None
+    dxpre, dW, db = linear_bwd(_lib.LGNN_GRAD_DIRECT, _f32c(dy), H=sv.y, act=sv.act, X=sv.x,
+                               W=sv.W, csr=csr, self_scale=sv.self_scale, want_dx=want_dx,
+                               want_db=sv.has_b)
+    dx = None
+    if want_dx:
+        dx = dxpre if csr is None else spmm_raw(csr.tptr, csr.tidx, csr.tw, sv.self_scale, dxpre)
+    return dx, dW, db
+
+
 class _NodeLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, graph, kind, self_scale, act):
-        _lib.require_gpu(x, W)
-        x, W = _f32c(x), _f32c(W)
-        b = _f32c(b) if b is not None else None
-        csr = graph.csr(kind) if graph is not None else None
-        y = linear_fwd(x, W, b, act, csr, self_scale)
-        ctx.save_for_backward(x, W, y)
-        ctx.graph, ctx.kind, ctx.self_scale, ctx.act = graph, kind, self_scale, act
-        ctx.has_b = b is not None
+        y, saved = node_linear_fwd(x, W, b, graph, kind, self_scale, act)
+        _save(ctx, saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, W, y = ctx.saved_tensors
-        csr = ctx.graph.csr(ctx.kind) if ctx.graph is not None else None
-        want_dx = ctx.needs_input_grad[0]
-        dxpre, dW, db = linear_bwd(_lib.LGNN_GRAD_DIRECT, _f32c(dy), H=y, act=ctx.act, X=x, W=W,
-                                   csr=csr, self_scale=ctx.self_scale, want_dx=want_dx,
-                                   want_db=ctx.has_b)
-        dx = None
-        if want_dx:
-            dx = dxpre if csr is None else spmm_raw(csr.tptr, csr.tidx, csr.tw, ctx.self_scale,
-                                                     dxpre)
-        return dx, dW, db, None, None, None, None
+        return (*node_linear_bwd(_load(ctx), dy, ctx.needs_input_grad[0]), None, None, None, None)
 
 
 def node_linear(x, W, b=None, graph: Graph | None = None, kind: str = "gcn",
@@ -899,6 +929,72 @@ def _bf16_operand(t: torch.Tensor) -> torch.Tensor:
     return tb if tb is not None else t.to(torch.bfloat16)
 
 
+class DensePlan(NamedTuple):
+    mfma: bool    # bf16 mode on the hand-written bf16 MFMA GEMMs (bflin.hip)
+    x_bf16: bool  # the compiled backward receives x rounded to bf16 (bf16 mode off those GEMMs)
+
+
+def dense_plan(N: int, bf16: bool) -> DensePlan:
+    mfma = bool(bf16) and bf16_mfma_fits(N)
+    return DensePlan(mfma, bool(bf16) and not mfma)
+
+
+# x: fp32, or the bf16 copy its producer wrote (mfma); wt: bf16 W^T from the forward's weight
+# prep (mfma, K <= 128) or None
+DenseSaved = namedtuple("DenseSaved", "x W wt bf16 has_b plan")
+
+
+def dense_linear_fwd(x, W, b, bf16, wp=None):
+    _lib.require_gpu(x, W)
+    x, W = _f32c(x), _f32c(W)
+    plan = dense_plan(W.size(0), bf16)
+    if plan.mfma:
+        # hand-written bf16 MFMA GEMM: an fp32 x is rounded as the kernel loads it (no copy);
+        # the output's bf16 copy feeds the next bf16 GEMM
+        xb = _bf16_copy_of(x)
+        A = xb if xb is not None else x
+        Wb, WTb = bf16_weight_operands(W, True)
+        y, yb = bf16_gemm(A, Wb, b, W.size(0), want_yb=BF16_OUT)
+        if yb is not None:
+            _remember_bf16(y, yb)
+        return y, DenseSaved(A, W, WTb, bf16, b is not None, plan)
+    # split-3 MFMA GEMM at fp32 accuracy (bf16 mode: RNE-rounded operands, N > 128)
+    y = dense_mm(x, wp if wp is not None else dense_planes(W, False, bf16), W.size(0), b, bf16)
+    return y, DenseSaved(x, W, None, bf16, b is not None, plan)
+
+
+def dense_linear_bwd(sv: DenseSaved, dy, want_dx: bool):
+    """(dx or None, dW, db or None)"""
+    x, W = sv.x, sv.W
+    dy = _f32c(dy)
+    N, K = W.shape
+    jobs = [] if sv.plan.mfma else None  # db's and dW's slab sums in one launch
+    db = None
+    if sv.has_b:  # from the column sums dy's producing GEMM wrote, when it was ours
+        db = colsum_of(dy, jobs)
+        if db is None and sv.plan.mfma:
+            db = dy.sum(0)
+    if sv.plan.mfma:
+        dyb = _bf16_operand(dy)
+        dW = bf16_wgrad(dyb, x, N, jobs)
+        reduce_multi(jobs, dW.device)
+        dx = None
+        if want_dx:
+            if K <= 128:
+                WTb = sv.wt if sv.wt is not None else bf16_weight_operands(W, True)[1]
+                dx, dxb = bf16_gemm(dyb, WTb, None, K, want_yb=BF16_OUT)
+                if dxb is not None:
+                    _remember_bf16(dx, dxb)
+            else:
+                dx = dense_mm(dyb, dense_planes(W, True, True), K, None, True)
+        return dx, dW, db
+    dW, db2 = dense_wgrad(dy, x, sv.bf16, want_db=sv.has_b and db is None)
+    if db is None and sv.has_b:
+        db = db2
+    dx = dense_mm(dy, dense_planes(W, True, sv.bf16), K, None, sv.bf16) if want_dx else None
+    return dx, dW, db
+
+
 class _DenseLinear(torch.autograd.Function):
     """y = x W^T + b for shapes outside the tile kernels (K > 128, K % 4 != 0: the reference's
     in_proj with 1025 input channels, gat.py:29 / lesions.py:142,169) or in bf16 mode, on the
@@ -909,62 +1005,13 @@ class _DenseLinear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, b, bf16, wp=None):
-        _lib.require_gpu(x, W)
-        x, W = _f32c(x), _f32c(W)
-        if bf16 and bf16_mfma_fits(W.size(0)):
-            # hand-written bf16 MFMA GEMM: an fp32 x is rounded as the kernel loads it (no copy);
-            # the output's bf16 copy feeds the next bf16 GEMM
-            xb = _bf16_copy_of(x)
-            A = xb if xb is not None else x
-            Wb, WTb = bf16_weight_operands(W, True)
-            y, yb = bf16_gemm(A, Wb, b, W.size(0), want_yb=BF16_OUT)
-            if yb is not None:
-                _remember_bf16(y, yb)
-            ctx.save_for_backward(A, W)
-            ctx.wt = WTb
-            ctx.bf16, ctx.has_b = bf16, b is not None
-            return y
-        # split-3 MFMA GEMM at fp32 accuracy (bf16 mode: RNE-rounded operands, N > 128)
-        y = dense_mm(x, wp if wp is not None else dense_planes(W, False, bf16), W.size(0), b,
-                     bf16)
-        ctx.save_for_backward(x, W)
-        ctx.bf16, ctx.has_b = bf16, b is not None
+        y, saved = dense_linear_fwd(x, W, b, bf16, wp)
+        _save(ctx, saved)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, W = ctx.saved_tensors
-        dy = _f32c(dy)
-        N, K = W.shape
-        mfma = ctx.bf16 and bf16_mfma_fits(N)
-        jobs = [] if mfma else None  # db's and dW's slab sums in one launch
-        db = None
-        if ctx.has_b:  # from the column sums dy's producing GEMM wrote, when it was ours
-            db = colsum_of(dy, jobs)
-            if db is None and mfma:
-                db = dy.sum(0)
-        if mfma:
-            dyb = _bf16_operand(dy)
-            dW = bf16_wgrad(dyb, x, N, jobs)
-            reduce_multi(jobs, dW.device)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                if K <= 128:
-                    WTb = getattr(ctx, "wt", None)
-                    if WTb is None:
-                        WTb = bf16_weight_operands(W, True)[1]
-                    dx, dxb = bf16_gemm(dyb, WTb, None, K, want_yb=BF16_OUT)
-                    if dxb is not None:
-                        _remember_bf16(dx, dxb)
-                else:
-                    dx = dense_mm(dyb, dense_planes(W, True, True), K, None, True)
-            return dx, dW, db, None, None
-        dW, db2 = dense_wgrad(dy, x, ctx.bf16, want_db=ctx.has_b and db is None)
-        if db is None and ctx.has_b:
-            db = db2
-        dx = dense_mm(dy, dense_planes(W, True, ctx.bf16), K, None, ctx.bf16) \
-            if ctx.needs_input_grad[0] else None
-        return dx, dW, db, None, None
+        return (*dense_linear_bwd(_load(ctx), dy, ctx.needs_input_grad[0]), None, None)
 
 
 def dense_linear(x, W, b=None, bf16: bool = False, wp=None):
@@ -1051,144 +1098,156 @@ def pool_head(x, Wout, bout, graph: Graph, mean: bool = True):
     return _PoolHead.apply(x, Wout, bout, graph, mean)
 
 
+class GcnPlan(NamedTuple):
+    fused: bool          # the fused stack forward (stack_fwd_planes): every width on the tiles
+    saved_s: tuple       # per conv: the forward saves S_l = Â H_{l-1} (else the backward gathers)
+    keeps_planes: bool   # the forward keeps the transposed weight planes: split-3 backward
+    fused_bwd: bool      # the fused backward (stack_bwd) when no input gradient is wanted
+    kind: str            # the graph build: "gcn_lazy" when only the fused kernels read it
+
+
+def gcn_plan(shapes: list, L: int, lazy_ok: bool = False) -> GcnPlan:
+    """shapes: (N, K) of W_in, W_1..W_L. lazy_ok: the forward builds the graph itself (a Graph,
+    not a compiled op's bundle) and no input gradient is wanted."""
+    fused = L + 1 <= STACK_MAX and all(fast_shape(K, N) for N, K in shapes)
+    saved_s = tuple(fused or fast_shape(K, N) or wide_shape(K, N) for N, K in shapes[1:])
+    keeps_planes = fused and MFMA_MODE == "s3" and BWD_S3 and L >= 1
+    fused_bwd = fused and FUSED_BWD and (1 <= L <= 2 or keeps_planes)
+    # only the fused kernels read this build: its transpose CSR is built only if a tile is open
+    kind = "gcn_lazy" if LAZY_TRANSPOSE and lazy_ok and fused_bwd else "gcn"
+    return GcnPlan(fused, saved_s, keeps_planes, fused_bwd, kind)
+
+
+# hs = [H_0..H_L]; ss = [S_1..S_L] (H_{l-1} itself where plan.saved_s[l] is False); params =
+# [W_in, b_in, (W_l, b_l) * L, W_out, b_out]; planes_t (plan.keeps_planes, else None): the
+# transposed weight planes (+ Â^T room); adjt: the forward's Â^T tiles when they have a buffer
+# of their own, else None
+GcnSaved = namedtuple("GcnSaved", "x pooled hs ss params planes_t adjt graph mean L plan")
+
+
+def gcn_stack_fwd(x, graph, mean, L, params, want_dx: bool, adjt_after_planes: bool = False):
+    """(logits, GcnSaved). adjt_after_planes: see stack_fwd_planes."""
+    _lib.require_gpu(x, *params)
+    x = _f32c(x)
+    params = [_f32c(p) for p in params]
+    W_in, b_in = params[0], params[1]
+    Ws = [params[2 * l] for l in range(L + 1)]
+    plan = gcn_plan([tuple(W.shape) for W in Ws], L,
+                    lazy_ok=isinstance(graph, Graph) and not want_dx)
+    planes_t = adjt = None
+    if plan.fused:  # builds the graph itself (with the weight-plane split riding along)
+        hs, ss, planes_t, adjt = stack_fwd_planes(
+            x, graph, Ws, [params[2 * l + 1] for l in range(L + 1)], plan.kind,
+            plan.keeps_planes, adjt_after_planes)
+    else:
+        csr = graph.csr(plan.kind)
+        hs = [linear_fwd(x, W_in, b_in, _lib.LGNN_ACT_NONE)]
+        ss = []  # aggregated conv inputs S_l = A_hat H_{l-1} (saved on the fast path)
+        for l in range(L):
+            W, b = params[2 + 2 * l], params[3 + 2 * l]
+            if plan.saved_s[l]:
+                h, s_ = linear_fwd(hs[-1], W, b, _lib.LGNN_ACT_ELU, csr, save_s=True)
+            else:
+                h, s_ = linear_fwd(hs[-1], W, b, _lib.LGNN_ACT_ELU, csr), hs[-1]
+            hs.append(h)
+            ss.append(s_)
+    W_out, b_out = params[2 + 2 * L], params[3 + 2 * L]
+    pooled, logits = pool_head_fwd(hs[-1], graph, mean, W_out, b_out)
+    return logits, GcnSaved(x, pooled, hs, ss, params, planes_t, adjt, graph, mean, L, plan)
+
+
+def gcn_fused_head(sv: GcnSaved, want_dx: bool) -> bool:
+    """True when the backward forms dP = dlogits W_out inside the single split-3 launch."""
+    return (sv.plan.fused_bwd and not want_dx and
+            head_in_stack_bwd(sv.graph, sv.L, sv.params[2 + 2 * sv.L].size(0),
+                              sv.planes_t is not None))
+
+
+def gcn_stack_bwd(sv: GcnSaved, dlogits, want_dx: bool, ce=None):
+    """(dx or None, [param gradients]). ce = (CeSrc, logits): the logits gradient is CE's,
+    formed where it is consumed (the fused backward's prologue, the out_proj reduction jobs) —
+    dlogits is None then."""
+    L, x, pooled, hs, ss, params, graph = sv.L, sv.x, sv.pooled, sv.hs, sv.ss, sv.params, sv.graph
+    kind = sv.plan.kind
+    csr = graph.csr(kind)
+    W_out = params[2 + 2 * L]
+    dlogits = _f32c(dlogits) if dlogits is not None else None
+    grads = [None] * len(params)
+    red: list = []
+    if sv.plan.fused_bwd and not want_dx:
+        Ws = [params[2 * l] for l in range(L + 1)]
+        if head_in_stack_bwd(graph, L, W_out.size(0), sv.planes_t is not None):
+            # dP is formed inside the stack kernel; out_proj's gradients (dlogits^T pooled,
+            # column sums of dlogits) join the stack's slab reductions: no head launch
+            C, D = W_out.shape
+            B = pooled.size(0)
+            dWo = torch.empty_like(W_out)
+            dbo = torch.empty(C, dtype=torch.float32, device=x.device)
+            part = CE_PART if ce is not None else dlogits
+            red += [(part, B, C * D, dWo, pooled, D), (part, B, C, dbo)]
+            outs = stack_bwd(None, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t,
+                             head=(ce[0] if ce is not None else dlogits, W_out), kind=kind,
+                             adjt_t=sv.adjt)
+        else:
+            dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
+            outs = stack_bwd(dp, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t, kind=kind,
+                             adjt_t=sv.adjt)
+        grads[2 + 2 * L], grads[3 + 2 * L] = dWo, dbo
+        for l, (dW, db) in enumerate(outs):
+            grads[2 * l], grads[2 * l + 1] = dW, db
+        reduce_multi(red, x.device, ce=ce[0] if ce is not None else None,
+                     num_classes=W_out.size(0))
+        return None, grads
+    assert ce is None, "the CE-formed logits gradient only on the fused head path"
+    dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
+    grads[2 + 2 * L], grads[3 + 2 * L] = dWo, dbo
+    if sv.plan.fused:  # the fused forward's S_l are not read here: S_l = Â H_{l-1} again
+        ss = [spmm_raw(csr.rowptr, csr.col, csr.w, 0.0, hs[l]) for l in range(L)]
+    dS = None
+    for l in reversed(range(L)):
+        W = params[2 + 2 * l]
+        if l == L - 1:
+            mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, None
+        else:
+            mode, dY, tc = _lib.LGNN_GRAD_TRANSPOSE, dS, csr
+        saved_s = sv.plan.saved_s[l]
+        dS, dW, db = linear_bwd(mode, dY, H=hs[l + 1], act=_lib.LGNN_ACT_ELU,
+                                X=ss[l] if saved_s else hs[l], W=W,
+                                csr=None if saved_s else csr, graph=graph,
+                                pool_mean=sv.mean, tcsr=tc, reducer=red)
+        grads[2 + 2 * l], grads[3 + 2 * l] = dW, db
+    # in_proj: dH0 = A^T dS_1 (transposed aggregation in the prologue); dx = dH0 W_in
+    if L > 0:
+        mode, dY, tc = _lib.LGNN_GRAD_TRANSPOSE, dS, csr
+    else:
+        mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, None
+    dx, dW, db = linear_bwd(mode, dY, H=None, act=_lib.LGNN_ACT_NONE, X=x, W=params[0],
+                            graph=graph, pool_mean=sv.mean, tcsr=tc, want_dx=want_dx,
+                            reducer=red)
+    reduce_multi(red, x.device)
+    grads[0], grads[1] = dW, db
+    return dx, grads
+
+
 class _GCNStack(torch.autograd.Function):
     """in_proj -> L x ELU(GCNConv) -> pool -> out_proj as one autograd node (dropout p = 0 or
     eval). params = [W_in, b_in, (W_l, b_l) * L, W_out, b_out]."""
 
     @staticmethod
     def forward(ctx, x, graph, mean, L, *params):
-        logits, to_save = _GCNStack._fwd(ctx, x, graph, mean, L, params)
-        ctx.save_for_backward(*to_save)
+        logits, saved = gcn_stack_fwd(x, graph, mean, L, params, ctx.needs_input_grad[0])
+        _save(ctx, saved)
         return logits
 
     @staticmethod
-    def _fwd(ctx, x, graph, mean, L, params):
-        _lib.require_gpu(x, *params)
-        x = _f32c(x)
-        params = [_f32c(p) for p in params]
-        W_in, b_in = params[0], params[1]
-        Ws = [params[2 * l] for l in range(L + 1)]
-        fused = L + 1 <= STACK_MAX and all(fast_shape(W.size(1), W.size(0)) for W in Ws)
-        keep = {} if fused and MFMA_MODE == "s3" and BWD_S3 and L >= 1 else None
-        # only the fused kernels read this build (the backward's fused path, the condition
-        # backward() tests): its transpose CSR is then built only if some tile is open
-        lazy = LAZY_TRANSPOSE and isinstance(graph, Graph) and fused and FUSED_BWD and \
-            (1 <= L <= 2 or keep is not None) and not ctx.needs_input_grad[0]
-        kind = "gcn_lazy" if lazy else "gcn"
-        ctx.kind = kind
-        # the fused forward builds the graph itself (with the weight-plane split riding along)
-        csr = None if fused else graph.csr(kind)
-        ctx.fused = fused
-        ctx.planes_t = None
-        ctx.adjt = None
-        if fused:
-            hs, ss = stack_fwd(x, graph, Ws, [params[2 * l + 1] for l in range(L + 1)], keep,
-                               kind)
-            ctx.planes_t = keep.get("planes_t") if keep else None
-            ctx.adjt = keep.get("adjt") if keep else None
-            ctx.saved_s = [True] * L
-        else:
-            hs = [linear_fwd(x, W_in, b_in, _lib.LGNN_ACT_NONE)]
-            ss = []  # aggregated conv inputs S_l = A_hat H_{l-1} (saved on the fast path)
-            ctx.saved_s = []
-            for l in range(L):
-                W, b = params[2 + 2 * l], params[3 + 2 * l]
-                fast = fast_shape(W.size(1), W.size(0)) or wide_shape(W.size(1), W.size(0))
-                if fast:
-                    h, s_ = linear_fwd(hs[-1], W, b, _lib.LGNN_ACT_ELU, csr, save_s=True)
-                else:
-                    h, s_ = linear_fwd(hs[-1], W, b, _lib.LGNN_ACT_ELU, csr), hs[-1]
-                hs.append(h)
-                ss.append(s_)
-                ctx.saved_s.append(fast)
-        W_out, b_out = params[2 + 2 * L], params[3 + 2 * L]
-        pooled, logits = pool_head_fwd(hs[-1], graph, mean, W_out, b_out)
-        ctx.graph, ctx.mean, ctx.L = graph, mean, L
-        ctx.n_saved = 2 + len(hs) + len(ss) + len(params)
-        return logits, (x, pooled, *hs, *ss, *params)
-
-    @staticmethod
     def backward(ctx, dlogits):
-        return _GCNStack._bwd(ctx, dlogits, ctx.saved_tensors)
-
-    @staticmethod
-    def fused_head(ctx, W_out) -> bool:
-        """True when the backward forms dP = dlogits W_out inside the single split-3 launch."""
-        return (ctx.fused and (1 <= ctx.L <= 2 or ctx.planes_t is not None) and
-                not ctx.needs_input_grad[0] and FUSED_BWD and
-                head_in_stack_bwd(ctx.graph, ctx.L, W_out.size(0), ctx.planes_t is not None))
-
-    @staticmethod
-    def _bwd(ctx, dlogits, saved, ce=None):
-        """ce = (CeSrc, logits): the logits gradient is CE's, formed where it is consumed (the
-        fused backward's prologue, the out_proj reduction jobs) — dlogits is None then."""
-        L = ctx.L
-        x, pooled = saved[0], saved[1]
-        hs = saved[2:3 + L]
-        ss = saved[3 + L:3 + 2 * L]
-        params = saved[3 + 2 * L:]
-        graph = ctx.graph
-        kind = getattr(ctx, "kind", "gcn")
-        csr = graph.csr(kind)
-        W_out = params[2 + 2 * L]
-        dlogits = _f32c(dlogits) if dlogits is not None else None
-        grads = [None] * len(params)
-        red: list = []
-        s3 = ctx.planes_t is not None
-        if ctx.fused and (1 <= L <= 2 or s3) and not ctx.needs_input_grad[0] and FUSED_BWD:
-            Ws = [params[2 * l] for l in range(L + 1)]
-            if head_in_stack_bwd(graph, L, W_out.size(0), s3):
-                # dP is formed inside the stack kernel; out_proj's gradients (dlogits^T pooled,
-                # column sums of dlogits) join the stack's slab reductions: no head launch
-                C, D = W_out.shape
-                B = pooled.size(0)
-                dWo = torch.empty_like(W_out)
-                dbo = torch.empty(C, dtype=torch.float32, device=x.device)
-                part = CE_PART if ce is not None else dlogits
-                red += [(part, B, C * D, dWo, pooled, D), (part, B, C, dbo)]
-                outs = stack_bwd(None, x, graph, ctx.mean, Ws, hs, ss, red, ctx.planes_t,
-                                 head=(ce[0] if ce is not None else dlogits, W_out), kind=kind,
-                                 adjt_t=getattr(ctx, "adjt", None))
-            else:
-                dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
-                outs = stack_bwd(dp, x, graph, ctx.mean, Ws, hs, ss, red, ctx.planes_t,
-                                 kind=kind, adjt_t=getattr(ctx, "adjt", None))
-            grads[2 + 2 * L], grads[3 + 2 * L] = dWo, dbo
-            for l, (dW, db) in enumerate(outs):
-                grads[2 * l], grads[2 * l + 1] = dW, db
-            reduce_multi(red, x.device, ce=ce[0] if ce is not None else None,
-                         num_classes=W_out.size(0))
-            return (None, None, None, None, *grads)
-        assert ce is None, "the CE-formed logits gradient only on the fused head path"
-        dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
-        grads[2 + 2 * L], grads[3 + 2 * L] = dWo, dbo
-        if ctx.fused:  # the fused forward saves no aggregated inputs: S_l = Â H_{l-1}
-            ss = [spmm_raw(csr.rowptr, csr.col, csr.w, 0.0, hs[l]) for l in range(L)]
-        dS = None
-        for l in reversed(range(L)):
-            W = params[2 + 2 * l]
-            if l == L - 1:
-                mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, None
-            else:
-                mode, dY, tc = _lib.LGNN_GRAD_TRANSPOSE, dS, csr
-            saved_s = ctx.saved_s[l]
-            dS, dW, db = linear_bwd(mode, dY, H=hs[l + 1], act=_lib.LGNN_ACT_ELU,
-                                    X=ss[l] if saved_s else hs[l], W=W,
-                                    csr=None if saved_s else csr, graph=graph,
-                                    pool_mean=ctx.mean, tcsr=tc, reducer=red)
-            grads[2 + 2 * l], grads[3 + 2 * l] = dW, db
-        # in_proj: dH0 = A^T dS_1 (transposed aggregation in the prologue); dx = dH0 W_in
-        want_dx = ctx.needs_input_grad[0]
-        if L > 0:
-            mode, dY, tc = _lib.LGNN_GRAD_TRANSPOSE, dS, csr
-        else:
-            mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, None
-        dx, dW, db = linear_bwd(mode, dY, H=None, act=_lib.LGNN_ACT_NONE, X=x, W=params[0],
-                                graph=graph, pool_mean=ctx.mean, tcsr=tc,
-                                want_dx=want_dx, reducer=red)
-        reduce_multi(red, x.device)
-        grads[0], grads[1] = dW, db
+        dx, grads = gcn_stack_bwd(_load(ctx), dlogits, ctx.needs_input_grad[0])
         return (dx, None, None, None, *grads)
+
+
+# stack: GcnSaved; z: logits; yy: int64 targets; out: (loss, sum of weights); w: class weights or
+# None; pm, wt: the logits gradient's factors (lgnn_ce_fwd_factors)
+CeSaved = namedtuple("CeSaved", "stack z yy lse out w pm wt")
 
 
 class _GCNStackCE(torch.autograd.Function):
@@ -1206,8 +1265,7 @@ class _GCNStackCE(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         yy = y.to(torch.int64).contiguous()
         w = _f32c(weight) if weight is not None else None
-        logits, to_save = _GCNStack._fwd(ctx, x, graph, mean, L, params)
-        z = logits
+        z, stack = gcn_stack_fwd(x, graph, mean, L, params, ctx.needs_input_grad[0])
         # one single-workgroup launch: loss, lse and the gradient's factors pm / wt
         B, C = z.shape
         dev = z.device
@@ -1219,42 +1277,34 @@ class _GCNStackCE(torch.autograd.Function):
         _lib.call("lgnn_ce_fwd_factors", _lib.ptr(z), _lib.ptr(yy), _lib.ptr(w), B, C,
                   _lib.ptr(lse), _lib.ptr(out), _lib.ptr(out) + 4, _lib.ptr(bad),
                   _lib.ptr(pm), _lib.ptr(wt), _s(dev))
-        ctx.ce_fwd = None
-        ctx.has_w = w is not None
-        ctx.has_pm = pm is not None
-        ctx.save_for_backward(*to_save, z, yy, lse, out, *((w,) if w is not None else ()),
-                              *((pm, wt) if pm is not None else ()))
-        return logits, out[0]
+        _save(ctx, CeSaved(stack, z, yy, lse, out, w, pm, wt))
+        return z, out[0]
 
     @staticmethod
     def backward(ctx, dlogits, dloss):
-        saved = ctx.saved_tensors
-        n = ctx.n_saved
-        stack_saved = saved[:n]
-        z, yy, lse, out = saved[n:n + 4]
-        w = saved[n + 4] if ctx.has_w else None
-        pm, wt = saved[-2:] if ctx.has_pm else (None, None)
-        params = stack_saved[3 + 2 * ctx.L:]
-        W_out = params[2 + 2 * ctx.L]
+        sv = _load(ctx)
+        want_dx = ctx.needs_input_grad[0]
 
-        def grads(r):  # _GCNStack's (dx, -, -, -, *param grads) -> this node's inputs
-            return (r[0], None, None, None, None, None, *r[4:])
+        def grads(r):  # gcn_stack_bwd's (dx, param grads) -> this node's inputs
+            return (r[0], None, None, None, None, None, *r[1])
 
         if dloss is None:
             if dlogits is None:
-                return (None,) * (6 + len(params))
-            return grads(_GCNStack._bwd(ctx, dlogits, stack_saved))
+                return (None,) * (6 + len(sv.stack.params))
+            return grads(gcn_stack_bwd(sv.stack, dlogits, want_dx))
         g = _f32c(dloss.reshape(1))
-        if dlogits is None and pm is not None and _GCNStack.fused_head(ctx, W_out):
-            src = _lib.CeSrc(pm.data_ptr(), wt.data_ptr(), out.data_ptr() + 4, g.data_ptr())
-            return grads(_GCNStack._bwd(ctx, None, stack_saved, ce=(src, z)))
-        B, C = z.shape
-        dz = torch.empty_like(z)
-        _lib.call("lgnn_ce_bwd", _lib.ptr(z), _lib.ptr(yy), _lib.ptr(w), B, C, _lib.ptr(lse),
-                  _lib.ptr(out) + 4, _lib.ptr(g), _lib.ptr(dz), _s(z.device))
+        if dlogits is None and gcn_fused_head(sv.stack, want_dx):
+            src = _lib.CeSrc(sv.pm.data_ptr(), sv.wt.data_ptr(), sv.out.data_ptr() + 4,
+                             g.data_ptr())
+            return grads(gcn_stack_bwd(sv.stack, None, want_dx, ce=(src, sv.z)))
+        B, C = sv.z.shape
+        dz = torch.empty_like(sv.z)
+        _lib.call("lgnn_ce_bwd", _lib.ptr(sv.z), _lib.ptr(sv.yy), _lib.ptr(sv.w), B, C,
+                  _lib.ptr(sv.lse), _lib.ptr(sv.out) + 4, _lib.ptr(g), _lib.ptr(dz),
+                  _s(sv.z.device))
         if dlogits is not None:
             dz = dz + dlogits
-        return grads(_GCNStack._bwd(ctx, dz, stack_saved))
+        return grads(gcn_stack_bwd(sv.stack, dz, want_dx))
 
 
 def gcn_stack_ce(x, graph: Graph, params: list[torch.Tensor], L: int, y: torch.Tensor,
@@ -1376,219 +1426,232 @@ def _global_count(M: int, group, dev, fixed=None) -> float:
     return float(t.item())
 
 
-class _GINConv(torch.autograd.Function):
+class GinPlan(NamedTuple):
+    bn_fused: bool  # BatchNorm inside the two linear launches (fast-path shapes)
+    gathered: bool  # generic kernels: no S saved, the backward gathers x again
+
+
+def gin_plan(K: int, N1: int, N2: int) -> GinPlan:
+    bn_fused = gin_bn_fused(K, N1, N2)
+    return GinPlan(bn_fused, not (bn_fused or fast_shape(K, N1) or wide_shape(K, N1)))
+
+
+# S = (1 + eps) x + A x, or x itself when plan.gathered; mask: dropout mask or None
+GinSaved = namedtuple("GinSaved", "S Z1 A1 H W1 W2 mean invstd scale shift mask graph self_scale "
+                                  "training count group act affine plan")
+
+
+def gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group=None,
+                 sync_count=None):
     """One GINConv(MLP([d1,d2,d2], act=ELU, norm=batch_norm)) with the model's F.elu fused:
         S  = (1 + eps) x_i + sum_{j->i} x_j      (eps = 0 buffer; edges as given, KNN loops kept)
         Z1 = S W1^T + b1;  A1 = ELU(BN(Z1)) [* dropout mask];  H = act(A1 W2^T + b2)
     Reference: gin.py:23 (GINConv(MLP(...))), gin.py:31 (F.elu). BN per `bn` (training uses batch
-    statistics; SyncBN over `group` when given)."""
-
-    @staticmethod
-    def forward(ctx, x, W1, b1, gamma, beta, W2, b2, graph, bn, training, eps, mask, act, group,
-                sync_count):
-        _lib.require_gpu(x, W1, W2)
-        x, W1, b1, W2, b2 = (_f32c(t) for t in (x, W1, b1, W2, b2))
-        csr = graph.csr("gin")
-        self_scale = 1.0 + float(eps)
-        M = x.size(0)
-        N1 = W1.size(0)
-        fast = fast_shape(W1.size(1), N1)
-        if gin_bn_fused(W1.size(1), N1, W2.size(0)):
-            H, saved = _GINConv._forward_fused(ctx, x, W1, b1, W2, b2, csr, self_scale, graph, bn,
-                                               training, mask, act, group, sync_count, gamma)
-            ctx.save_for_backward(*saved)
-            return H
-        if fast or wide_shape(W1.size(1), N1):
-            Z1, S = linear_fwd(x, W1, b1, _lib.LGNN_ACT_NONE, csr, self_scale, save_s=True)
+    statistics; SyncBN over `group` when given). Returns (H, the batch statistics' fp64 sums or
+    None in eval, GinSaved)."""
+    _lib.require_gpu(x, W1, W2)
+    x, W1, b1, W2, b2 = (_f32c(t) for t in (x, W1, b1, W2, b2))
+    csr = graph.csr("gin")
+    self_scale = 1.0 + float(eps)
+    M, N1 = x.size(0), W1.size(0)
+    dev = x.device
+    plan = gin_plan(W1.size(1), N1, W2.size(0))
+    count = float(M)
+    sums = None
+    if plan.bn_fused and training:
+        # BatchNorm folded into the two linear launches (lgnn_node_linear_fwd_bn): the BN
+        # statistics in the first one's epilogue, BN + ELU (+ mask) in the second one's prologue.
+        # Same arithmetic as the unfused sequence except the fixed order of the fp64 sums.
+        P = _lib.load().lgnn_bn_fused_partials(M)
+        Z1 = torch.empty(M, N1, dtype=torch.float32, device=dev)
+        S = torch.empty_like(x)
+        part = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
+        _lib.call("lgnn_node_linear_fwd_bn", _lib.ptr(x), M, x.size(1), _lib.ptr(csr.rowptr),
+                  _lib.ptr(csr.col), _lib.ptr(csr.w), float(self_scale), W1.data_ptr(),
+                  _lib.ptr(b1), N1, _lib.LGNN_ACT_NONE, _lib.ptr(Z1), _lib.ptr(S),
+                  _lib.ptr(part), None, None, None, None, _s(dev))
+        sums = torch.empty(2 * N1, dtype=torch.float64, device=dev)
+        count = _global_count(M, group, dev, sync_count)
+        if count <= 1:
+            raise ValueError("Expected more than 1 value per channel when training")
+        if group is None:  # sums + the BN constants in one launch
+            mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev,
+                                                     part=(part, P))
         else:
-            Z1, S = linear_fwd(x, W1, b1, _lib.LGNN_ACT_NONE, csr, self_scale), None
-        count = float(M)
-        sums = None
+            from .dist import sync_all_reduce
+
+            _lib.call("lgnn_bn_partials_reduce", _lib.ptr(part), P, N1, _lib.ptr(sums), None,
+                      None, _s(dev))
+            sync_all_reduce(sums, group)
+            mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev)
+    else:
+        if plan.gathered:
+            Z1, S = linear_fwd(x, W1, b1, _lib.LGNN_ACT_NONE, csr, self_scale), x
+        else:
+            Z1, S = linear_fwd(x, W1, b1, _lib.LGNN_ACT_NONE, csr, self_scale, save_s=True)
         if training:
             sums = bn_stats(Z1)
-            count = _global_count(M, group, x.device, sync_count)
+            count = _global_count(M, group, dev, sync_count)
             if count <= 1:
                 raise ValueError("Expected more than 1 value per channel when training")
             if group is not None:
                 from .dist import sync_all_reduce
 
                 sync_all_reduce(sums, group)
-        mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, x.device)
-        A1 = bn_act(Z1, scale, shift, mask)
-        H = linear_fwd(A1, W2, b2, act)
-        ctx.save_for_backward(x if S is None else S, Z1, A1, H, W1, W2, mean, invstd, scale,
-                              shift, mask)
-        ctx.graph, ctx.self_scale, ctx.gathered = graph, self_scale, S is None
-        ctx.training, ctx.count, ctx.group, ctx.act = training, count, group, act
-        ctx.bn_sums = sums  # the batch statistics' sums (library.py: running-stat update op)
-        ctx.affine = gamma is not None
-        return H
-
-    @staticmethod
-    def _forward_fused(ctx, x, W1, b1, W2, b2, csr, self_scale, graph, bn, training, mask, act,
-                       group, sync_count, gamma):
-        """BatchNorm folded into the two linear launches (lgnn_node_linear_fwd_bn): the BN
-        statistics in the first one's epilogue, BN + ELU (+ mask) in the second one's prologue.
-        Same arithmetic as the unfused sequence except the fixed order of the fp64 sums."""
-        M, N1 = x.size(0), W1.size(0)
-        dev = x.device
-        P = _lib.load().lgnn_bn_fused_partials(M)
-        Z1 = torch.empty(M, N1, dtype=torch.float32, device=dev)
-        S = torch.empty_like(x)
-        count = float(M)
-        sums = None
-        fname = "lgnn_node_linear_fwd_bn"
-        w1, w2 = W1.data_ptr(), W2.data_ptr()
-        if training:
-            part = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
-            _lib.call(fname, _lib.ptr(x), M, x.size(1), _lib.ptr(csr.rowptr),
-                      _lib.ptr(csr.col), _lib.ptr(csr.w), float(self_scale), w1,
-                      _lib.ptr(b1), N1, _lib.LGNN_ACT_NONE, _lib.ptr(Z1), _lib.ptr(S),
-                      _lib.ptr(part), None, None, None, None, _s(dev))
-            sums = torch.empty(2 * N1, dtype=torch.float64, device=dev)
-            count = _global_count(M, group, dev, sync_count)
-            if count <= 1:
-                raise ValueError("Expected more than 1 value per channel when training")
-            if group is None:  # sums + the BN constants in one launch
-                mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev,
-                                                         part=(part, P))
-            else:
-                from .dist import sync_all_reduce
-
-                _lib.call("lgnn_bn_partials_reduce", _lib.ptr(part), P, N1, _lib.ptr(sums), None,
-                          None, _s(dev))
-                sync_all_reduce(sums, group)
-                mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev)
-        else:
-            Z1, S = linear_fwd(x, W1, b1, _lib.LGNN_ACT_NONE, csr, self_scale, save_s=True)
-            mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev)
+        mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev)
+    if plan.bn_fused:
         A1 = torch.empty_like(Z1)
         N2 = W2.size(0)
         H = torch.empty(M, N2, dtype=torch.float32, device=dev)
-        _lib.call(fname, _lib.ptr(Z1), M, N1, None, None, None, 0.0, w2, _lib.ptr(b2), N2, act,
-                  _lib.ptr(H), None, None, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mask),
-                  _lib.ptr(A1), _s(dev))
-        ctx.graph, ctx.self_scale, ctx.gathered = graph, self_scale, False
-        ctx.training, ctx.count, ctx.group, ctx.act = training, count, group, act
-        ctx.bn_sums = sums
-        ctx.affine = gamma is not None
-        ctx.bn_fused = True
-        return H, (S, Z1, A1, H, W1, W2, mean, invstd, scale, shift, mask)
+        _lib.call("lgnn_node_linear_fwd_bn", _lib.ptr(Z1), M, N1, None, None, None, 0.0,
+                  W2.data_ptr(), _lib.ptr(b2), N2, act, _lib.ptr(H), None, None, _lib.ptr(scale),
+                  _lib.ptr(shift), _lib.ptr(mask), _lib.ptr(A1), _s(dev))
+    else:
+        A1 = bn_act(Z1, scale, shift, mask)
+        H = linear_fwd(A1, W2, b2, act)
+    return H, sums, GinSaved(S, Z1, A1, H, W1, W2, mean, invstd, scale, shift, mask, graph,
+                             self_scale, training, count, group, act, bn.affine, plan)
 
-    @staticmethod
-    def _backward_fused(ctx, dH, pool: tuple | None = None, gather: tuple | None = None,
-                        defer_dx: bool = False, extra_red: list | None = None):
-        """pool = (dlogits, W_out, graph, mean): the output gradient comes from the pooled readout
-        (global pool + out_proj backward folded into Lin2's backward load; dH is None).
-        gather = (dS, tself): the output gradient is the next conv's aggregation backward,
-        tself dS + A^T dS, gathered as Lin2's backward loads it (dH is None). defer_dx: return
-        this conv's pre-aggregation input gradient (for the previous layer to gather) instead
-        of aggregating it here. extra_red: more slab / outer-product jobs for this conv's
-        reduction launch."""
-        S, Z1, A1, H, W1, W2, mean, invstd, scale, shift, mask = ctx.saved_tensors[:11]
-        csr = ctx.graph.csr("gin")
-        M, N1 = Z1.shape
-        N2 = W2.size(0)
-        K = S.size(1)
-        dev = Z1.device
-        P = _lib.load().lgnn_bn_fused_partials(M)
-        red: list = []
-        fname = "lgnn_node_linear_bwd_bn"
-        w1, w2 = W1.data_ptr(), W2.data_ptr()
-        # Lin2 backward; its dX (= dA1) epilogue also sums the BN backward's (g, g xhat)
-        dA1 = torch.empty_like(Z1)
-        slab2 = torch.empty(P * (N2 * N1 + N2), dtype=torch.float32, device=dev)
-        gpart = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
-        if gather is not None:
-            dS, tself = gather
-            _lib.call("lgnn_node_linear_bwd_bn_gather", _lib.ptr(dS), _lib.ptr(csr.tptr),
-                      _lib.ptr(csr.tidx), _lib.ptr(csr.tw), float(tself), _lib.ptr(H), ctx.act,
-                      _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                      _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                      _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                      _lib.ptr(gpart), _s(dev))
-        elif pool is not None:
-            dlog, W_out, pg, pmean = pool
-            _lib.call("lgnn_node_linear_bwd_bn_pool", _lib.LGNN_BN_GSTATS, None, _lib.ptr(H),
-                      ctx.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                      _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                      _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                      _lib.ptr(gpart), None, 0.0, int(ctx.training), _lib.ptr(pg.batch),
-                      _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
-                      W_out.size(0), _s(dev))
-        else:
-            _lib.call(fname, _lib.LGNN_BN_GSTATS, _lib.ptr(_f32c(dH)), _lib.ptr(H),
-                      ctx.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                      _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                      _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                      _lib.ptr(gpart), None, 0.0, int(ctx.training), _s(dev))
-        dW2 = torch.empty(N2, N1, dtype=torch.float32, device=dev)
-        db2 = torch.empty(N2, dtype=torch.float32, device=dev)
-        red += [(slab2[:P * N2 * N1], P, N2 * N1, dW2), (slab2[P * N2 * N1:], P, N2, db2)]
-        local = torch.empty(2 * N1, dtype=torch.float64, device=dev)
-        dg = dbt = None
-        if ctx.affine:  # the affine gradients come out of the same launch (local sums)
-            dg = torch.empty(N1, dtype=torch.float32, device=dev)
-            dbt = torch.empty(N1, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_bn_partials_reduce", _lib.ptr(gpart), P, N1, _lib.ptr(local),
-                  _lib.ptr(dg), _lib.ptr(dbt), _s(dev))
+
+def gin_conv_bwd(sv: GinSaved, dH, want_dx: bool, pool: tuple | None = None,
+                 gather: tuple | None = None, defer_dx: bool = False,
+                 extra_red: list | None = None):
+    """(dx, dW1, db1, dgamma, dbeta, dW2, db2). On the BN-fused path only:
+    pool = (dlogits, W_out, graph, mean): the output gradient comes from the pooled readout
+    (global pool + out_proj backward folded into Lin2's backward load; dH is None).
+    gather = (dS, tself): the output gradient is the next conv's aggregation backward,
+    tself dS + A^T dS, gathered as Lin2's backward loads it (dH is None). defer_dx: return
+    this conv's pre-aggregation input gradient (for the previous layer to gather) instead
+    of aggregating it here. extra_red: more slab / outer-product jobs for this conv's
+    reduction launch."""
+    S, Z1, A1, H, W1, W2, mask = sv.S, sv.Z1, sv.A1, sv.H, sv.W1, sv.W2, sv.mask
+    mean, invstd, scale, shift = sv.mean, sv.invstd, sv.scale, sv.shift
+    csr = sv.graph.csr("gin")
+    if not sv.plan.bn_fused:
+        assert pool is None and gather is None and not defer_dx and not extra_red
+        dA1, dW2, db2 = linear_bwd(_lib.LGNN_GRAD_DIRECT, _f32c(dH), H=H, act=sv.act, X=A1, W=W2)
+        local = bn_bwd_stats(dA1, Z1, mask, scale, shift, mean, invstd)
         sums = local
-        if ctx.training and ctx.group is not None:
+        if sv.training and sv.group is not None:
             from .dist import sync_all_reduce
 
             sums = local.clone()
-            sync_all_reduce(sums, ctx.group)
-        # Lin1 backward with the BN backward applied to dA1 as it is loaded
-        want_dx = ctx.needs_input_grad[0]
-        dxpre = torch.empty(M, K, dtype=torch.float32, device=dev) if want_dx else None
-        slab1 = torch.empty(P * (N1 * K + N1), dtype=torch.float32, device=dev)
-        _lib.call(fname, _lib.LGNN_BN_GIN, _lib.ptr(dA1), None,
-                  _lib.LGNN_ACT_NONE, _lib.ptr(S), M, K, w1, N1, _lib.ptr(dxpre),
-                  _lib.ptr(slab1), _lib.ptr(slab1[P * N1 * K:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), None,
-                  _lib.ptr(sums), float(ctx.count), int(ctx.training), _s(dev))
-        dW1 = torch.empty(N1, K, dtype=torch.float32, device=dev)
-        db1 = torch.empty(N1, dtype=torch.float32, device=dev)
-        red += [(slab1[:P * N1 * K], P, N1 * K, dW1), (slab1[P * N1 * K:], P, N1, db1)]
-        if extra_red:  # e.g. out_proj's dW / db as outer-product jobs (no k_head_bwd launch)
-            red += extra_red
-        reduce_multi(red, dev)
-        dx = None
-        if want_dx:
-            dx = dxpre if defer_dx else spmm_raw(csr.tptr, csr.tidx, csr.tw, ctx.self_scale,
-                                                 dxpre)
-        return (dx, dW1, db1, dg, dbt, dW2, db2, None, None, None, None, None, None, None,
-                None)
+            sync_all_reduce(sums, sv.group)
+        dZ1, dg, dbt = bn_bwd_apply(dA1, Z1, mask, scale, shift, mean, invstd, sums, sv.count,
+                                    sv.training, local, sv.affine)
+        dxpre, dW1, db1 = linear_bwd(_lib.LGNN_GRAD_DIRECT, dZ1, H=None, act=_lib.LGNN_ACT_NONE,
+                                     X=S, W=W1, csr=csr if sv.plan.gathered else None,
+                                     self_scale=sv.self_scale if sv.plan.gathered else 0.0,
+                                     want_dx=want_dx)
+        dx = spmm_raw(csr.tptr, csr.tidx, csr.tw, sv.self_scale, dxpre) if want_dx else None
+        return dx, dW1, db1, dg, dbt, dW2, db2
+    M, N1 = Z1.shape
+    N2 = W2.size(0)
+    K = S.size(1)
+    dev = Z1.device
+    P = _lib.load().lgnn_bn_fused_partials(M)
+    red: list = []
+    fname = "lgnn_node_linear_bwd_bn"
+    w1, w2 = W1.data_ptr(), W2.data_ptr()
+    # Lin2 backward; its dX (= dA1) epilogue also sums the BN backward's (g, g xhat)
+    dA1 = torch.empty_like(Z1)
+    slab2 = torch.empty(P * (N2 * N1 + N2), dtype=torch.float32, device=dev)
+    gpart = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
+    if gather is not None:
+        dS, tself = gather
+        _lib.call("lgnn_node_linear_bwd_bn_gather", _lib.ptr(dS), _lib.ptr(csr.tptr),
+                  _lib.ptr(csr.tidx), _lib.ptr(csr.tw), float(tself), _lib.ptr(H), sv.act,
+                  _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
+                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
+                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
+                  _lib.ptr(gpart), _s(dev))
+    elif pool is not None:
+        dlog, W_out, pg, pmean = pool
+        _lib.call("lgnn_node_linear_bwd_bn_pool", _lib.LGNN_BN_GSTATS, None, _lib.ptr(H),
+                  sv.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
+                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
+                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
+                  _lib.ptr(gpart), None, 0.0, int(sv.training), _lib.ptr(pg.batch),
+                  _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
+                  W_out.size(0), _s(dev))
+    else:
+        _lib.call(fname, _lib.LGNN_BN_GSTATS, _lib.ptr(_f32c(dH)), _lib.ptr(H),
+                  sv.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
+                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
+                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
+                  _lib.ptr(gpart), None, 0.0, int(sv.training), _s(dev))
+    dW2 = torch.empty(N2, N1, dtype=torch.float32, device=dev)
+    db2 = torch.empty(N2, dtype=torch.float32, device=dev)
+    red += [(slab2[:P * N2 * N1], P, N2 * N1, dW2), (slab2[P * N2 * N1:], P, N2, db2)]
+    local = torch.empty(2 * N1, dtype=torch.float64, device=dev)
+    dg = dbt = None
+    if sv.affine:  # the affine gradients come out of the same launch (local sums)
+        dg = torch.empty(N1, dtype=torch.float32, device=dev)
+        dbt = torch.empty(N1, dtype=torch.float32, device=dev)
+    _lib.call("lgnn_bn_partials_reduce", _lib.ptr(gpart), P, N1, _lib.ptr(local),
+              _lib.ptr(dg), _lib.ptr(dbt), _s(dev))
+    sums = local
+    if sv.training and sv.group is not None:
+        from .dist import sync_all_reduce
+
+        sums = local.clone()
+        sync_all_reduce(sums, sv.group)
+    # Lin1 backward with the BN backward applied to dA1 as it is loaded
+    dxpre = torch.empty(M, K, dtype=torch.float32, device=dev) if want_dx else None
+    slab1 = torch.empty(P * (N1 * K + N1), dtype=torch.float32, device=dev)
+    _lib.call(fname, _lib.LGNN_BN_GIN, _lib.ptr(dA1), None,
+              _lib.LGNN_ACT_NONE, _lib.ptr(S), M, K, w1, N1, _lib.ptr(dxpre),
+              _lib.ptr(slab1), _lib.ptr(slab1[P * N1 * K:]), P, _lib.ptr(Z1), _lib.ptr(mask),
+              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), None,
+              _lib.ptr(sums), float(sv.count), int(sv.training), _s(dev))
+    dW1 = torch.empty(N1, K, dtype=torch.float32, device=dev)
+    db1 = torch.empty(N1, dtype=torch.float32, device=dev)
+    red += [(slab1[:P * N1 * K], P, N1 * K, dW1), (slab1[P * N1 * K:], P, N1, db1)]
+    if extra_red:  # e.g. out_proj's dW / db as outer-product jobs (no k_head_bwd launch)
+        red += extra_red
+    reduce_multi(red, dev)
+    dx = None
+    if want_dx:
+        dx = dxpre if defer_dx else spmm_raw(csr.tptr, csr.tidx, csr.tw, sv.self_scale,
+                                             dxpre)
+    return dx, dW1, db1, dg, dbt, dW2, db2
+
+
+class _GINConv(torch.autograd.Function):
+    """gin_conv_fwd / gin_conv_bwd as an autograd node; gamma / beta are bn's affine parameters
+    (inputs so that they receive gradients)."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, gamma, beta, W2, b2, graph, bn, training, eps, mask, act, group,
+                sync_count):
+        H, _, saved = gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group,
+                                   sync_count)
+        _save(ctx, saved)
+        return H
 
     @staticmethod
     def backward(ctx, dH):
-        if getattr(ctx, "bn_fused", False):
-            return _GINConv._backward_fused(ctx, dH)
-        S, Z1, A1, H, W1, W2, mean, invstd, scale, shift, mask = ctx.saved_tensors
-        csr = ctx.graph.csr("gin")
-        dA1, dW2, db2 = linear_bwd(_lib.LGNN_GRAD_DIRECT, _f32c(dH), H=H, act=ctx.act, X=A1, W=W2)
-        local = bn_bwd_stats(dA1, Z1, mask, scale, shift, mean, invstd)
-        sums = local
-        if ctx.training and ctx.group is not None:
-            from .dist import sync_all_reduce
+        return (*gin_conv_bwd(_load(ctx), dH, ctx.needs_input_grad[0]),) + (None,) * 8
 
-            sums = local.clone()
-            sync_all_reduce(sums, ctx.group)
-        dZ1, dg, dbt = bn_bwd_apply(dA1, Z1, mask, scale, shift, mean, invstd, sums, ctx.count,
-                                    ctx.training, local, ctx.affine)
-        want_dx = ctx.needs_input_grad[0]
-        if ctx.gathered:
-            dxpre, dW1, db1 = linear_bwd(_lib.LGNN_GRAD_DIRECT, dZ1, H=None,
-                                         act=_lib.LGNN_ACT_NONE, X=S, W=W1, csr=csr,
-                                         self_scale=ctx.self_scale, want_dx=want_dx)
-        else:
-            dxpre, dW1, db1 = linear_bwd(_lib.LGNN_GRAD_DIRECT, dZ1, H=None,
-                                         act=_lib.LGNN_ACT_NONE, X=S, W=W1, want_dx=want_dx)
-        dx = None
-        if want_dx:
-            dx = spmm_raw(csr.tptr, csr.tidx, csr.tw, ctx.self_scale, dxpre)
-        return (dx, dW1, db1, dg, dbt, dW2, db2, None, None, None, None, None, None, None,
-                None)
+
+# a model's last conv (conv: GinSaved or GatSaved) with its readout, global pool + out_proj
+HeadSaved = namedtuple("HeadSaved", "conv pooled W_out mean")
+
+
+def _head_grads(sv, dlogits, jobs: bool):
+    """out_proj's (dW, db) buffers and either the outer-product jobs that fill them in a
+    layer's slab reduction (no k_head_bwd launch) or, with jobs False, lgnn_pool_head_bwd."""
+    pooled, W_out = sv.pooled, sv.W_out
+    B, D = pooled.shape
+    C = W_out.size(0)
+    dev = pooled.device
+    dWo = torch.empty(C, D, dtype=torch.float32, device=dev)
+    dbo = torch.empty(C, dtype=torch.float32, device=dev)
+    if jobs:
+        return dWo, dbo, [(dlogits, B, C * D, dWo, pooled, D), (dlogits, B, C, dbo)]
+    _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D, _lib.ptr(W_out),
+              C, None, _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
+    return dWo, dbo, None
 
 
 class _GINConvHead(torch.autograd.Function):
@@ -1601,31 +1664,22 @@ class _GINConvHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, b1, gamma, beta, W2, b2, W_out, b_out, graph, bn, training, eps,
                 mask, act, group, sync_count, mean):
-        _lib.require_gpu(x, W1, W2, W_out)
-        x, W1, b1, W2, b2 = (_f32c(t) for t in (x, W1, b1, W2, b2))
+        _lib.require_gpu(W_out)
         W_out, b_out = _f32c(W_out), _f32c(b_out)
-        csr = graph.csr("gin")
-        H, saved = _GINConv._forward_fused(ctx, x, W1, b1, W2, b2, csr, 1.0 + float(eps), graph,
-                                           bn, training, mask, act, group, sync_count, gamma)
+        H, _, conv = gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group,
+                                  sync_count)
         pooled, logits = pool_head_fwd(H, graph, mean, W_out, b_out)
-        ctx.save_for_backward(*saved, pooled, W_out)
-        ctx.head_graph, ctx.head_mean = graph, mean
+        _save(ctx, HeadSaved(conv, pooled, W_out, mean))
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        pooled, W_out = ctx.saved_tensors[11:13]
+        sv = _load(ctx)
         dlogits = _f32c(dlogits)
-        B, D = pooled.shape
-        C = W_out.size(0)
-        dev = pooled.device
-        dWo = torch.empty(C, D, dtype=torch.float32, device=dev)
-        dbo = torch.empty(C, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D,
-                  _lib.ptr(W_out), C, None, _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
-        g = _GINConv._backward_fused(ctx, None, pool=(dlogits, W_out, ctx.head_graph,
-                                                      ctx.head_mean))
-        return (*g[:7], dWo, dbo) + (None,) * 9
+        dWo, dbo, _ = _head_grads(sv, dlogits, jobs=False)
+        g = gin_conv_bwd(sv.conv, None, ctx.needs_input_grad[0],
+                         pool=(dlogits, sv.W_out, sv.conv.graph, sv.mean))
+        return (*g, dWo, dbo) + (None,) * 9
 
 
 # out_proj's dW / db as outer-product jobs of a layer's slab reduction (GIN / GAT model nodes);
@@ -1633,16 +1687,8 @@ class _GINConvHead(torch.autograd.Function):
 HEAD_JOBS = True
 
 
-class _SubCtx:
-    """The per-conv state _GINConv._forward_fused / _backward_fused keep on an autograd ctx,
-    for one conv inside the _GINStack node."""
-
-    def __init__(self, needs_dx: bool):
-        self.needs_input_grad = (needs_dx,)
-        self.saved_tensors = ()
-
-    def save_for_backward(self, *t):
-        self.saved_tensors = t
+# convs: GinSaved of every conv but the last; head: HeadSaved of the last
+GinStackSaved = namedtuple("GinStackSaved", "x W_in convs head")
 
 
 class _GINStack(torch.autograd.Function):
@@ -1657,67 +1703,47 @@ class _GINStack(torch.autograd.Function):
     def forward(ctx, x, graph, mean, specs, W_in, b_in, W_out, b_out, *flat):
         _lib.require_gpu(x, W_in, W_out)
         x, W_in, b_in, W_out, b_out = (_f32c(t) for t in (x, W_in, b_in, W_out, b_out))
-        csr = graph.csr("gin")
+        graph.csr("gin")  # the graph build before in_proj
         h = linear_fwd(x, W_in, b_in, _lib.LGNN_ACT_NONE)
-        subs, saved = [], [x, W_in]
+        convs = []
         for i, sp in enumerate(specs):
-            W1, b1, gamma, beta, W2, b2 = flat[6 * i:6 * i + 6]
-            sub = _SubCtx(True)
-            h, sv = _GINConv._forward_fused(sub, h, _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2),
-                                            csr, 1.0 + float(sp["eps"]), graph, sp["bn"],
-                                            sp["training"], sp["mask"], sp["act"], sp["group"],
-                                            sp["sync_count"], gamma)
-            sub.n_saved = len(sv)
-            saved += list(sv)
-            subs.append(sub)
+            W1, b1, _gamma, _beta, W2, b2 = flat[6 * i:6 * i + 6]
+            h, _, conv = gin_conv_fwd(h, W1, b1, W2, b2, graph, sp["bn"], sp["training"],
+                                      sp["eps"], sp["mask"], sp["act"], sp["group"],
+                                      sp["sync_count"])
+            convs.append(conv)
         pooled, logits = pool_head_fwd(h, graph, mean, W_out, b_out)
-        ctx.save_for_backward(*saved, pooled, W_out)
-        ctx.subs, ctx.graph, ctx.mean = subs, graph, mean
-        ctx.in_self = [1.0 + float(sp["eps"]) for sp in specs]
+        _save(ctx, GinStackSaved(x, W_in, convs[:-1], HeadSaved(convs[-1], pooled, W_out, mean)))
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        saved = ctx.saved_tensors
-        x, W_in = saved[0], saved[1]
-        pooled, W_out = saved[-2], saved[-1]
+        sv = _load(ctx)
+        convs = [*sv.convs, sv.head.conv]
+        graph = sv.head.conv.graph
         dlogits = _f32c(dlogits)
-        B, D = pooled.shape
-        C = W_out.size(0)
-        dev = pooled.device
-        dWo = torch.empty(C, D, dtype=torch.float32, device=dev)
-        dbo = torch.empty(C, dtype=torch.float32, device=dev)
         # out_proj's dW = dlogits^T pooled and db = colsum dlogits join the last conv's slab
         # reductions (outer-product jobs): no k_head_bwd launch
-        head_jobs = [(dlogits, B, C * D, dWo, pooled, D), (dlogits, B, C, dbo)]
-        if not HEAD_JOBS:
-            _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D,
-                      _lib.ptr(W_out), C, None, _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
-            head_jobs = None
-        off = 2
-        for sub in ctx.subs:
-            sub.saved_tensors = saved[off:off + sub.n_saved]
-            off += sub.n_saved
-        L = len(ctx.subs)
+        dWo, dbo, head_jobs = _head_grads(sv.head, dlogits, HEAD_JOBS)
+        L = len(convs)
         grads = [None] * L
         dS = None
         # each layer's dW / db slabs are summed right after that layer, while they are still in
         # the caches (one launch at the end measured 10 us slower per C4 step)
         for i in range(L - 1, -1, -1):
-            sub = ctx.subs[i]
             if i == L - 1:
-                g = _GINConv._backward_fused(sub, None, pool=(dlogits, W_out, ctx.graph,
-                                                               ctx.mean), defer_dx=True,
-                                             extra_red=head_jobs)
+                g = gin_conv_bwd(convs[i], None, True, defer_dx=True, extra_red=head_jobs,
+                                 pool=(dlogits, sv.head.W_out, graph, sv.head.mean))
             else:
-                g = _GINConv._backward_fused(sub, None, gather=(dS, ctx.in_self[i + 1]),
-                                             defer_dx=True)
+                g = gin_conv_bwd(convs[i], None, True, defer_dx=True,
+                                 gather=(dS, convs[i + 1].self_scale))
             dS = g[0]
-            grads[i] = g[1:7]
+            grads[i] = g[1:]
         # in_proj: its output gradient is the first conv's aggregation backward, gathered
         dx, dW_in, db_in = linear_bwd(_lib.LGNN_GRAD_TRANSPOSE, dS, H=None, act=_lib.LGNN_ACT_NONE,
-                                      X=x, W=W_in, tcsr=ctx.graph.csr("gin"),
-                                      tself=ctx.in_self[0], want_dx=ctx.needs_input_grad[0])
+                                      X=sv.x, W=sv.W_in, tcsr=graph.csr("gin"),
+                                      tself=convs[0].self_scale,
+                                      want_dx=ctx.needs_input_grad[0])
         flat = [t for g in grads for t in g]
         return (dx, None, None, None, dW_in, db_in, dWo, dbo, *flat)
 
@@ -1789,166 +1815,217 @@ def gin_conv(x, W1, b1, bn, W2, b2, graph: Graph, eps: float = 0.0, mask=None,
 # ----------------------------------------------------------------------------------------------
 
 
-class _GATConv(torch.autograd.Function):
+class GatPlan(NamedTuple):
+    dense: bool   # lin on the dense MFMA GEMMs (split-3, or bf16-rounded) instead of the tiles
+    mfma: bool    # bf16 mode on the hand-written bf16 MFMA GEMMs (bflin.hip)
+    scored: bool  # the attention scores come out of the lin GEMM's epilogue (no lgnn_gat_att)
+
+
+def gat_plan(K: int, HC: int, bf16: bool) -> GatPlan:
+    # fp32: the lin on the split-3 MFMA GEMMs (s3gemm.hip) at every width — they beat the
+    # fp32-MFMA tile kernels (2.7x the MFMA rate at fp32 accuracy); GAT_S3 = False: tiles
+    dense = bool(bf16) or not fast_shape(K, HC) or GAT_S3
+    mfma = bool(bf16) and bf16_mfma_fits(HC)
+    scored = GAT_GEMM_ATT and (64 < K <= 128 if mfma else dense and not bf16 and HC <= 128)
+    return GatPlan(dense, mfma, scored)
+
+
+# x: fp32, or the bf16 copy its producer wrote (mfma); att_src / att_dst flat [H * C]; wt: bf16
+# W^T from the forward's weight prep (mfma) or None; wpt: W^T's split-3 planes for dx
+# (s3_weight_bundle) or None
+GatSaved = namedtuple("GatSaved", "x W att_src att_dst XP a_s a_d alpha Y mask wt wpt graph heads "
+                                  "slope act bf16 has_bias plan")
+
+
+def gat_conv_fwd(x, W, att_src, att_dst, bias, graph, heads, slope, mask, act, bf16=False,
+                 wp=None, wpt=None):
     """PyG 2.5.1 GATConv (reference gat.py:31) + the model's F.elu (gat.py:51):
         XP = x W^T (lin, no bias) viewed [M, H, C];  a_s = <XP, att_src>, a_d = <XP, att_dst>
         alpha = softmax_dst(leaky_relu(a_s[j] + a_d[i]));  out_i = sum_j alpha_ij mask_ij XP_j
         Y = act(out.view(M, H*C) + bias)
-    over remove_self_loops + add_self_loops of edge_index (graph kind "gat")."""
+    over remove_self_loops + add_self_loops of edge_index (graph kind "gat").
+    Returns (Y, GatSaved)."""
+    _lib.require_gpu(x, W, att_src, att_dst)
+    x, W = _f32c(x), _f32c(W)
+    att_src, att_dst = _f32c(att_src).view(-1), _f32c(att_dst).view(-1)
+    bias = _f32c(bias) if bias is not None else None
+    csr = graph.csr("gat")
+    M = x.size(0)
+    HC = W.size(0)
+    C = HC // heads
+    dev = x.device
+    plan = gat_plan(W.size(1), HC, bf16)
+    wt = None
+    if plan.mfma:  # hand-written bf16 MFMA lin; x rounded in the kernel unless a copy exists
+        xb = _bf16_copy_of(x)
+        xg, Wg = (xb if xb is not None else x), W
+        Wb, wt = bf16_weight_operands(W, True)
+    else:  # fp32, or bf16 wider than 128: the operands are split / rounded in the GEMMs
+        xg, Wg = x, W
+    a_s = torch.empty(M, heads, dtype=torch.float32, device=dev)
+    a_d = torch.empty(M, heads, dtype=torch.float32, device=dev)
+    if plan.mfma and plan.scored:
+        # the attention scores come out of the lin GEMM's epilogue (no lgnn_gat_att pass)
+        XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
+        xg = xg.contiguous()
+        _lib.call("lgnn_bf16_gemm_att", _lib.ptr(xg), int(xg.dtype == torch.float32), M,
+                  xg.size(1),
+                  _lib.ptr(Wb), HC, _lib.ptr(XP), None, _lib.ptr(att_src), _lib.ptr(att_dst),
+                  heads, C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+    elif plan.mfma:
+        XP = bf16_gemm(xg, Wb, None, HC)[0]
+    elif plan.scored:
+        # split-3 (or one rounded plane) with the attention scores in the GEMM's epilogue
+        XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
+        xg = xg.contiguous()
+        _lib.call("lgnn_s3_gemm_att", _lib.ptr(xg), M, xg.size(1),
+                  _lib.ptr(wp if wp is not None else dense_planes(Wg, False, False)), HC, 3,
+                  _lib.ptr(XP), _lib.ptr(att_src), _lib.ptr(att_dst), heads,
+                  C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+    elif plan.dense:  # split-3 MFMA GEMM (fp32 accuracy), or one rounded plane in bf16 mode
+        XP = dense_mm(xg, wp if wp is not None else dense_planes(Wg, False, bf16), HC, None,
+                      bf16)
+    else:
+        XP = linear_fwd(x, W, None, _lib.LGNN_ACT_NONE)
+    if not plan.scored:
+        _lib.call("lgnn_gat_att", _lib.ptr(XP), M, heads, C, _lib.ptr(att_src),
+                  _lib.ptr(att_dst), _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+    cap = csr.col.numel()
+    alpha = torch.empty(cap, heads, dtype=torch.float32, device=dev)
+    Y = torch.empty(M, HC, dtype=torch.float32, device=dev)
+    # bf16 mode: the kernel also writes Y in bf16 for the next layer's GEMM (no cast pass)
+    Yb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) if bf16 and BF16_OUT else None
+    _lib.call("lgnn_gat_fwd", _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(XP),
+              _lib.ptr(a_s), _lib.ptr(a_d), M, heads, C, float(slope), _lib.ptr(mask),
+              _lib.ptr(bias), act, _lib.ptr(alpha), _lib.ptr(Y), _lib.ptr(Yb), _s(dev))
+    if Yb is not None:
+        _remember_bf16(Y, Yb)
+    return Y, GatSaved(xg, Wg, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, wt, wpt, graph,
+                       heads, slope, act, bf16, bias is not None, plan)
 
-    @staticmethod
-    def forward(ctx, x, W, att_src, att_dst, bias, graph, heads, slope, mask, act, bf16=False,
-                wp=None, wpt=None):
-        _lib.require_gpu(x, W, att_src, att_dst)
-        x, W = _f32c(x), _f32c(W)
-        att_src, att_dst = _f32c(att_src).view(-1), _f32c(att_dst).view(-1)
-        bias = _f32c(bias) if bias is not None else None
-        csr = graph.csr("gat")
-        M = x.size(0)
-        HC = W.size(0)
-        C = HC // heads
-        dev = x.device
-        # fp32: the lin on the split-3 MFMA GEMMs (s3gemm.hip) at every width — they beat the
-        # fp32-MFMA tile kernels (2.7x the MFMA rate at fp32 accuracy); GAT_S3 = False: tiles
-        dense = bf16 or not fast_shape(W.size(1), HC) or GAT_S3
-        mfma = bf16 and bf16_mfma_fits(HC)
-        ctx.wt = None
-        if mfma:  # hand-written bf16 MFMA lin; x rounded in the kernel unless a copy exists
-            xb = _bf16_copy_of(x)
-            xg, Wg = (xb if xb is not None else x), W
-            Wb, ctx.wt = bf16_weight_operands(W, True)
-        else:  # fp32, or bf16 wider than 128: the operands are split / rounded in the GEMMs
-            xg, Wg = x, W
-        a_s = torch.empty(M, heads, dtype=torch.float32, device=dev)
-        a_d = torch.empty(M, heads, dtype=torch.float32, device=dev)
-        scored = False
-        if mfma and GAT_GEMM_ATT and 64 < xg.size(1) <= 128:
-            # the attention scores come out of the lin GEMM's epilogue (no lgnn_gat_att pass)
-            XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
-            xg = xg.contiguous()
-            _lib.call("lgnn_bf16_gemm_att", _lib.ptr(xg), int(xg.dtype == torch.float32), M,
-                      xg.size(1),
-                      _lib.ptr(Wb), HC, _lib.ptr(XP), None, _lib.ptr(att_src), _lib.ptr(att_dst),
-                      heads, C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
-            scored = True
-        elif mfma:
-            XP = bf16_gemm(xg, Wb, None, HC)[0]
-        elif dense and not bf16 and GAT_GEMM_ATT and HC <= 128:
-            # split-3 (or one rounded plane) with the attention scores in the GEMM's epilogue
-            XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
-            xg = xg.contiguous()
-            _lib.call("lgnn_s3_gemm_att", _lib.ptr(xg), M, xg.size(1),
-                      _lib.ptr(wp if wp is not None else dense_planes(Wg, False, False)), HC, 3,
-                      _lib.ptr(XP), _lib.ptr(att_src), _lib.ptr(att_dst), heads,
-                      C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
-            scored = True
-        elif dense:  # split-3 MFMA GEMM (fp32 accuracy), or one rounded plane in bf16 mode
-            XP = dense_mm(xg, wp if wp is not None else dense_planes(Wg, False, bf16), HC, None,
-                          bf16)
-        else:
-            XP = linear_fwd(x, W, None, _lib.LGNN_ACT_NONE)
-        if not scored:
-            _lib.call("lgnn_gat_att", _lib.ptr(XP), M, heads, C, _lib.ptr(att_src),
-                      _lib.ptr(att_dst), _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
-        cap = csr.col.numel()
-        alpha = torch.empty(cap, heads, dtype=torch.float32, device=dev)
-        Y = torch.empty(M, HC, dtype=torch.float32, device=dev)
-        # bf16 mode: the kernel also writes Y in bf16 for the next layer's GEMM (no cast pass)
-        Yb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) if bf16 and BF16_OUT else None
-        _lib.call("lgnn_gat_fwd", _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(XP),
-                  _lib.ptr(a_s), _lib.ptr(a_d), M, heads, C, float(slope), _lib.ptr(mask),
-                  _lib.ptr(bias), act, _lib.ptr(alpha), _lib.ptr(Y), _lib.ptr(Yb), _s(dev))
-        ctx.save_for_backward(xg, Wg, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask)
-        ctx.graph, ctx.heads, ctx.slope, ctx.act = graph, heads, slope, act
-        ctx.bf16, ctx.dense = bf16, dense
-        ctx.wpt = wpt if dense and not mfma else None  # W^T's planes for dx (s3_weight_bundle)
-        ctx.has_bias = bias is not None
-        ctx.att_shape = (1, heads, C)
-        if Yb is not None:
-            _remember_bf16(Y, Yb)
-        return Y
 
-    @staticmethod
-    def backward(ctx, dY, pool: tuple | None = None, extra_red: list | None = None):
-        """pool = (dlogits, W_out, graph, mean): the output gradient is formed from the readout's
-        gradient inside the edge kernel (lgnn_gat_bwd_edge_pool; dY is None). extra_red: more
-        slab / outer-product jobs for this layer's reduction launch."""
-        x, W, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask = ctx.saved_tensors[:10]
-        csr = ctx.graph.csr("gat")
-        M, HC = Y.shape
-        H = ctx.heads
-        C = HC // H
-        dev = Y.device
-        dZ = torch.empty_like(Y)
-        da_e = torch.empty_like(alpha)
-        da_d = torch.empty(M, H, dtype=torch.float32, device=dev)
-        if pool is not None:
-            dlog, W_out, pg, pmean = pool
-            _lib.call("lgnn_gat_bwd_edge_pool", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
-                      _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha), _lib.ptr(mask),
-                      _lib.ptr(Y), ctx.act, M, H, C, float(ctx.slope), _lib.ptr(pg.batch),
-                      _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
-                      W_out.size(0), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
-        else:
-            _lib.call("lgnn_gat_bwd_edge", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
-                      _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha),
-                      _lib.ptr(mask), _lib.ptr(_f32c(dY)), _lib.ptr(Y), ctx.act, M, H, C,
-                      float(ctx.slope), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
-        P = _lib.load().lgnn_gat_bwd_num_partials(M)
-        part = torch.empty(P * 3 * HC, dtype=torch.float32, device=dev)
-        dXP = torch.empty_like(XP)
-        # bf16 MFMA lin: the kernel also writes dXP in bf16 (the GEMMs' operand, no cast pass)
-        dXPb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) \
-            if ctx.bf16 and bf16_mfma_fits(HC) and BF16_OUT else None
-        _lib.call("lgnn_gat_bwd_node", _lib.ptr(csr.tptr), _lib.ptr(csr.tidx),
-                  _lib.ptr(csr.tmap), _lib.ptr(alpha), _lib.ptr(mask), _lib.ptr(da_e),
-                  _lib.ptr(da_d), _lib.ptr(dZ), _lib.ptr(XP), _lib.ptr(att_src),
-                  _lib.ptr(att_dst), M, H, C, _lib.ptr(dXP), _lib.ptr(part), P, _lib.ptr(dXPb),
-                  _s(dev))
-        red = torch.empty(3 * HC, dtype=torch.float32, device=dev)
-        want_dx = ctx.needs_input_grad[0]
-        if ctx.bf16 and bf16_mfma_fits(HC):
-            dg = dXPb if dXPb is not None else dXP.to(torch.bfloat16)
-            # the attention partials and lin's dW slabs summed in one launch
-            jobs = [(part, P, 3 * HC, red)] + (extra_red or [])
-            dW = bf16_wgrad(dg, x, HC, jobs)
+def gat_conv_bwd(sv: GatSaved, dY, want_dx: bool, pool: tuple | None = None,
+                 extra_red: list | None = None):
+    """(dx or None, dW, red): red is the one reduction buffer [datt_src | datt_dst | dbias]
+    (att_grads splits it). pool = (dlogits, W_out, graph, mean): the output gradient is formed
+    from the readout's gradient inside the edge kernel (lgnn_gat_bwd_edge_pool; dY is None).
+    extra_red: more slab / outer-product jobs for this layer's reduction launch."""
+    x, W, att_src, att_dst, XP = sv.x, sv.W, sv.att_src, sv.att_dst, sv.XP
+    a_s, a_d, alpha, Y, mask = sv.a_s, sv.a_d, sv.alpha, sv.Y, sv.mask
+    csr = sv.graph.csr("gat")
+    M, HC = Y.shape
+    H = sv.heads
+    C = HC // H
+    dev = Y.device
+    dZ = torch.empty_like(Y)
+    da_e = torch.empty_like(alpha)
+    da_d = torch.empty(M, H, dtype=torch.float32, device=dev)
+    if pool is not None:
+        dlog, W_out, pg, pmean = pool
+        _lib.call("lgnn_gat_bwd_edge_pool", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+                  _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha), _lib.ptr(mask),
+                  _lib.ptr(Y), sv.act, M, H, C, float(sv.slope), _lib.ptr(pg.batch),
+                  _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
+                  W_out.size(0), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
+    else:
+        _lib.call("lgnn_gat_bwd_edge", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+                  _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha),
+                  _lib.ptr(mask), _lib.ptr(_f32c(dY)), _lib.ptr(Y), sv.act, M, H, C,
+                  float(sv.slope), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
+    P = _lib.load().lgnn_gat_bwd_num_partials(M)
+    part = torch.empty(P * 3 * HC, dtype=torch.float32, device=dev)
+    dXP = torch.empty_like(XP)
+    # bf16 MFMA lin: the kernel also writes dXP in bf16 (the GEMMs' operand, no cast pass)
+    dXPb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) \
+        if sv.plan.mfma and BF16_OUT else None
+    _lib.call("lgnn_gat_bwd_node", _lib.ptr(csr.tptr), _lib.ptr(csr.tidx),
+              _lib.ptr(csr.tmap), _lib.ptr(alpha), _lib.ptr(mask), _lib.ptr(da_e),
+              _lib.ptr(da_d), _lib.ptr(dZ), _lib.ptr(XP), _lib.ptr(att_src),
+              _lib.ptr(att_dst), M, H, C, _lib.ptr(dXP), _lib.ptr(part), P, _lib.ptr(dXPb),
+              _s(dev))
+    red = torch.empty(3 * HC, dtype=torch.float32, device=dev)
+    if sv.plan.mfma:
+        dg = dXPb if dXPb is not None else dXP.to(torch.bfloat16)
+        # the attention partials and lin's dW slabs summed in one launch
+        jobs = [(part, P, 3 * HC, red)] + (extra_red or [])
+        dW = bf16_wgrad(dg, x, HC, jobs)
+        reduce_multi(jobs, dev)
+        dx = None
+        if want_dx:
+            K = W.size(1)
+            if K <= 128:
+                WTb = sv.wt if sv.wt is not None else bf16_weight_operands(W, True)[1]
+                # dx's column sums ride along: the in_proj backward's bias gradient
+                dx, dxb = bf16_gemm(dg, WTb, None, K, want_yb=BF16_OUT, want_colsum=True)
+                if dxb is not None:
+                    _remember_bf16(dx, dxb)
+            else:
+                dx = dense_mm(dg, dense_planes(W, True, True), K, None, True)
+    else:
+        jobs = [(part, P, 3 * HC, red)] + (extra_red or [])
+        if sv.plan.dense:  # split-3 (or bf16-rounded) MFMA GEMMs on the fp32 dXP
+            # lin's dW slabs join the attention partials' reduction: one launch per conv
+            dW = dense_wgrad(dXP, x, sv.bf16, reducer=jobs)[0]
             reduce_multi(jobs, dev)
             dx = None
             if want_dx:
-                K = W.size(1)
-                if K <= 128:
-                    WTb = getattr(ctx, "wt", None)
-                    if WTb is None:
-                        WTb = bf16_weight_operands(W, True)[1]
-                    # dx's column sums ride along: the in_proj backward's bias gradient
-                    dx, dxb = bf16_gemm(dg, WTb, None, K, want_yb=BF16_OUT, want_colsum=True)
-                    if dxb is not None:
-                        _remember_bf16(dx, dxb)
-                else:
-                    dx = dense_mm(dg, dense_planes(W, True, True), K, None, True)
+                wpt = sv.wpt if sv.wpt is not None else dense_planes(W, True, sv.bf16)
+                dx = dense_mm(dXP, wpt, W.size(1), None, sv.bf16)
         else:
-            jobs = [(part, P, 3 * HC, red)] + (extra_red or [])
-            if ctx.dense:  # split-3 (or bf16-rounded) MFMA GEMMs on the fp32 dXP
-                # lin's dW slabs join the attention partials' reduction: one launch per conv
-                dW = dense_wgrad(dXP, x, ctx.bf16, reducer=jobs)[0]
+            if extra_red:
                 reduce_multi(jobs, dev)
-                wpt = getattr(ctx, "wpt", None)
-                dx = dense_mm(dXP, wpt if wpt is not None else dense_planes(W, True, ctx.bf16),
-                              W.size(1), None, ctx.bf16) if want_dx else None
             else:
-                if extra_red:
-                    reduce_multi(jobs, dev)
-                else:
-                    _lib.call("lgnn_reduce_partials", _lib.ptr(part), P, 3 * HC, _lib.ptr(red),
-                              _s(dev))
-                dx, dW, _ = linear_bwd(_lib.LGNN_GRAD_DIRECT, dXP, H=None,
-                                       act=_lib.LGNN_ACT_NONE, X=x, W=W, want_dx=want_dx,
-                                       want_db=False)
-        ctx.red = red  # the compiled path returns the one buffer (lgnn::gat_conv_bwd)
-        datt_s = red[:HC].view(ctx.att_shape)
-        datt_d = red[HC:2 * HC].view(ctx.att_shape)
-        dbias = red[2 * HC:] if ctx.has_bias else None
-        return dx, dW, datt_s, datt_d, dbias, None, None, None, None, None, None, None, None
+                _lib.call("lgnn_reduce_partials", _lib.ptr(part), P, 3 * HC, _lib.ptr(red),
+                          _s(dev))
+            dx, dW, _ = linear_bwd(_lib.LGNN_GRAD_DIRECT, dXP, H=None,
+                                   act=_lib.LGNN_ACT_NONE, X=x, W=W, want_dx=want_dx,
+                                   want_db=False)
+    return dx, dW, red
+
+
+def att_grads(red: torch.Tensor, heads: int, has_bias: bool):
+    """(datt_src, datt_dst, dbias or None) [1, H, C] / [H * C]: views of gat_conv_bwd's one
+    reduction buffer (no copies)."""
+    HC = red.numel() // 3
+    shape = (1, heads, HC // heads)
+    return (red[:HC].view(shape), red[HC:2 * HC].view(shape), red[2 * HC:] if has_bias else None)
+
+
+def gat_head_fwd(x, W, att_src, att_dst, bias, W_out, b_out, graph, heads, slope, mask, act,
+                 bf16, mean, wp=None, wpt=None):
+    """The last GATConv + global pool + out_proj: (logits, HeadSaved)."""
+    Y, conv = gat_conv_fwd(x, W, att_src, att_dst, bias, graph, heads, slope, mask, act, bf16, wp,
+                           wpt)
+    W_out, b_out = _f32c(W_out), _f32c(b_out)
+    pooled, logits = pool_head_fwd(Y, graph, mean, W_out, b_out)
+    return logits, HeadSaved(conv, pooled, W_out, mean)
+
+
+def gat_head_bwd(sv: HeadSaved, dlogits, want_dx: bool):
+    """(dx or None, dW, red, dW_out, db_out): the readout's backward formed inside the edge
+    kernel's load (lgnn_gat_bwd_edge_pool), no dH tensor; out_proj's dW / db as outer-product
+    jobs of the layer's reduction (HEAD_JOBS)."""
+    dlogits = _f32c(dlogits)
+    dWo, dbo, head_jobs = _head_grads(sv, dlogits, HEAD_JOBS)
+    dx, dW, red = gat_conv_bwd(sv.conv, None, want_dx, extra_red=head_jobs,
+                               pool=(dlogits, sv.W_out, sv.conv.graph, sv.mean))
+    return dx, dW, red, dWo, dbo
+
+
+class _GATConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, W, att_src, att_dst, bias, graph, heads, slope, mask, act, bf16=False,
+                wp=None, wpt=None):
+        Y, saved = gat_conv_fwd(x, W, att_src, att_dst, bias, graph, heads, slope, mask, act,
+                                bf16, wp, wpt)
+        _save(ctx, saved)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        sv = _load(ctx)
+        dx, dW, red = gat_conv_bwd(sv, dY, ctx.needs_input_grad[0])
+        return (dx, dW, *att_grads(red, sv.heads, sv.has_bias)) + (None,) * 8
 
 
 GAT_S3 = True
@@ -1987,39 +2064,16 @@ class _GATConvHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, att_src, att_dst, bias, W_out, b_out, graph, heads, slope, mask, act,
                 bf16, mean, wp=None, wpt=None):
-        sub = _SubCtx(True)
-        Y = _GATConv.forward(sub, x, W, att_src, att_dst, bias, graph, heads, slope, mask, act,
-                             bf16, wp, wpt)
-        W_out, b_out = _f32c(W_out), _f32c(b_out)
-        pooled, logits = pool_head_fwd(Y, graph, mean, W_out, b_out)
-        ctx.save_for_backward(*sub.saved_tensors, pooled, W_out)
-        sub.saved_tensors = ()
-        ctx.sub, ctx.head_graph, ctx.head_mean = sub, graph, mean
+        logits, saved = gat_head_fwd(x, W, att_src, att_dst, bias, W_out, b_out, graph, heads,
+                                     slope, mask, act, bf16, mean, wp, wpt)
+        _save(ctx, saved)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        saved = ctx.saved_tensors
-        pooled, W_out = saved[10], saved[11]
-        dlogits = _f32c(dlogits)
-        B, D = pooled.shape
-        C = W_out.size(0)
-        dev = pooled.device
-        dWo = torch.empty(C, D, dtype=torch.float32, device=dev)
-        dbo = torch.empty(C, dtype=torch.float32, device=dev)
-        sub = ctx.sub
-        sub.saved_tensors = saved[:10]
-        sub.needs_input_grad = (ctx.needs_input_grad[0],)
-        # out_proj's dW / db as outer-product jobs of the layer's reduction (no k_head_bwd)
-        head_jobs = [(dlogits, B, C * D, dWo, pooled, D), (dlogits, B, C, dbo)]
-        if not HEAD_JOBS:
-            _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D,
-                      _lib.ptr(W_out), C, None, _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
-            head_jobs = None
-        g = _GATConv.backward(sub, None, pool=(dlogits, W_out, ctx.head_graph, ctx.head_mean),
-                              extra_red=head_jobs)
-        sub.saved_tensors = ()
-        return (*g[:5], dWo, dbo) + (None,) * 9
+        sv = _load(ctx)
+        dx, dW, red, dWo, dbo = gat_head_bwd(sv, dlogits, ctx.needs_input_grad[0])
+        return (dx, dW, *att_grads(red, sv.conv.heads, sv.conv.has_bias), dWo, dbo) + (None,) * 9
 
 
 def gat_conv_head(x, W, att_src, att_dst, bias, W_out, b_out, graph: Graph, heads: int,
@@ -2148,36 +2202,46 @@ def cross_entropy(logits, target, weight=None, validate: bool = False):
 # ----------------------------------------------------------------------------------------------
 
 
-class _SortPool(torch.autograd.Function):
-    """PyG 2.5.1 SortAggregation(k) (reference drgnet.py:37,59) on lgnn_sort_pool_fwd/_bwd."""
+SortSaved = namedtuple("SortSaved", "x rank fill graph k")
 
+
+def sort_pool_fwd(x, graph, k):
+    """PyG 2.5.1 SortAggregation(k) (reference drgnet.py:37,59) on lgnn_sort_pool_fwd/_bwd:
+    (out, SortSaved)."""
+    _lib.require_gpu(x)
+    x = _f32c(x)
+    M, D = x.shape
+    B = graph.num_graphs
+    dev = x.device
+    out = torch.empty(B, k * D, dtype=torch.float32, device=dev)
+    rank = torch.empty(M, dtype=torch.int32, device=dev)
+    fill = torch.empty(1, dtype=torch.float32, device=dev)
+    nws = _lib.load().lgnn_sort_pool_workspace_bytes()
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    _lib.call("lgnn_sort_pool_fwd", _lib.ptr(x), M, D, _lib.ptr(graph.gptr), B, int(k),
+              _lib.ptr(out), _lib.ptr(rank), _lib.ptr(fill), _lib.ptr(ws), nws, _s(dev))
+    return out, SortSaved(x, rank, fill, graph, int(k))
+
+
+def sort_pool_bwd(sv: SortSaved, dout):
+    M, D = sv.x.shape
+    dx = torch.empty_like(sv.x)
+    _lib.call("lgnn_sort_pool_bwd", _lib.ptr(_f32c(dout)), _lib.ptr(sv.x), _lib.ptr(sv.rank),
+              _lib.ptr(sv.graph.batch), _lib.ptr(sv.fill), M, D, sv.k, _lib.ptr(dx),
+              _s(sv.x.device))
+    return dx
+
+
+class _SortPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, graph, k):
-        _lib.require_gpu(x)
-        x = _f32c(x)
-        M, D = x.shape
-        B = graph.num_graphs
-        dev = x.device
-        out = torch.empty(B, k * D, dtype=torch.float32, device=dev)
-        rank = torch.empty(M, dtype=torch.int32, device=dev)
-        fill = torch.empty(1, dtype=torch.float32, device=dev)
-        nws = _lib.load().lgnn_sort_pool_workspace_bytes()
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        _lib.call("lgnn_sort_pool_fwd", _lib.ptr(x), M, D, _lib.ptr(graph.gptr), B, int(k),
-                  _lib.ptr(out), _lib.ptr(rank), _lib.ptr(fill), _lib.ptr(ws), nws, _s(dev))
-        ctx.save_for_backward(x, rank, fill)
-        ctx.graph, ctx.k = graph, int(k)
+        out, saved = sort_pool_fwd(x, graph, k)
+        _save(ctx, saved)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, rank, fill = ctx.saved_tensors
-        M, D = x.shape
-        dx = torch.empty_like(x)
-        _lib.call("lgnn_sort_pool_bwd", _lib.ptr(_f32c(dout)), _lib.ptr(x), _lib.ptr(rank),
-                  _lib.ptr(ctx.graph.batch), _lib.ptr(fill), M, D, ctx.k, _lib.ptr(dx),
-                  _s(x.device))
-        return dx, None, None
+        return sort_pool_bwd(_load(ctx), dout), None, None
 
 
 def sort_pool(x, graph: Graph, k: int):

@@ -114,6 +114,58 @@ def test_compiled_model_matches_eager_and_oracle(cuda, name):
     assert torch._dynamo.utils.counters["stats"]["unique_graphs"] <= 2  # no per-size recompile
 
 
+# Shape classes off the 128-wide fast path: every path decision the eager forward takes (dense /
+# tile / generic kernels, which S_l are saved, BatchNorm fused or not, planes kept or not) must be
+# the one the compiled ops take. name -> (model, kwargs, d_in, classes, {ops switch: value})
+OFF_FAST_PATH = {
+    "gin_wide_mixed": (GIN, dict(hidden=[64, 160, 64]), 96, 3, {}),
+    "gin_generic": (GIN, dict(hidden=[64, 160, 64]), 96, 3, {"WIDE": "f32"}),
+    "gin_unfused_bn": (GIN, dict(hidden=[128, 128]), 128, 5, {"BN_FUSED": False}),
+    "gcn_layerwise": (GCN, dict(hidden=[160, 64]), 128, 5, {}),
+    "gcn_layerwise_generic": (GCN, dict(hidden=[160, 64]), 128, 5, {"WIDE": "f32"}),
+    "gcn_fused_no_planes": (GCN, dict(hidden=[128, 128, 128]), 128, 5, {"MFMA_MODE": "f32"}),
+    "gat_wide_fp32": (GAT, dict(hidden=[256, 256], heads=4), 64, 5, {}),
+    "gat_wide_bf16": (GAT, dict(hidden=[256, 256], heads=4, precision="bf16"), 64, 5, {}),
+    "gat_tiles": (GAT, dict(hidden=[128, 128], heads=4), 64, 5, {"GAT_S3": False}),
+}
+
+
+@pytest.mark.parametrize("name", list(OFF_FAST_PATH))
+def test_compiled_matches_eager_off_the_fast_path(cuda, monkeypatch, name):
+    """One training step, eager and compiled, on ragged graphs: logits and every gradient
+    bitwise equal."""
+    from lesion_gnn_amd import ops
+
+    cls, kw, d_in, classes, switches = OFF_FAST_PATH[name]
+    for k, v in switches.items():
+        monkeypatch.setattr(ops, k, v)
+    # the switches are module state no compile cache keys on: a graph cached by another case
+    # (same model, other switches) would carry that case's output shapes
+    import torch._functorch.config
+    import torch._inductor.config
+
+    monkeypatch.setattr(torch._inductor.config, "fx_graph_cache", False)
+    monkeypatch.setattr(torch._functorch.config, "enable_autograd_cache", False)
+    kw = dict(kw)
+    hidden = kw.pop("hidden")
+    torch.manual_seed(1234)
+    if cls is GAT:
+        m = GAT(d_in, hidden, classes, dropout=0.0, **kw).train()
+    else:
+        m = cls(d_in, hidden, classes, 0.0, **kw).train()
+    sizes = [1, 5, 64, 200, 2, 33, 90, 17]
+    b = synth.make_batch(len(sizes), k=6, d_in=d_in, num_classes=classes, seed=5, sizes=sizes)
+    eager = clone_to(m, cuda)
+    torch._dynamo.reset()
+    compiled = torch.compile(clone_to(m, cuda), dynamic=True, fullgraph=True)
+    lc, gc = step(compiled, b, cuda)
+    le, ge = step(eager, b, cuda)
+    gc = strip(gc)
+    assert torch.equal(lc, le), (lc - le).abs().max()
+    for k in ge:
+        assert torch.equal(gc[k], ge[k]), k
+
+
 def test_compiled_dropout_model_is_one_graph(cuda):
     """The reference experiment trains the compiled GAT with dropout 0.35 (configs/config.py:
     52-65): with fullgraph=True a graph break (round 5: the mask scale's fp32 rounding went

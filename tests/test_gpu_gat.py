@@ -113,7 +113,7 @@ def test_gat_alpha_rows_sum_to_one(cuda):
     g = Graph(b.edge_index.to(cuda), b.num_nodes)
     conv = m.convs[0]
     x = torch.randn(b.num_nodes, 64, device=cuda)
-    ctxout = ops._GATConv.forward  # noqa: F841 (documented entry)
+    ctxout = ops.gat_conv_fwd  # noqa: F841 (documented entry)
     csr = g.csr("gat")
     y = ops.gat_conv(x, conv.lin.weight, conv.att_src, conv.att_dst, conv.bias, g, 4)
     assert torch.isfinite(y).all()

@@ -32,10 +32,8 @@ def main(n: int = 200) -> None:
     W_out = torch.randn(5, D, device=dev, generator=gen) / 11.3
     dlog = torch.randn(b.num_graphs, 5, device=dev, generator=gen)
     dS_ws = torch.empty(2 * M * 128, device=dev)
-    keep: dict = {}
-    ops.stack_fwd(b.x, g, Ws, [torch.zeros(D, device=dev)] * (L + 1), keep)
-    planes_t = keep["planes_t"]
-    adjt = keep.get("adjt")
+    _, _, planes_t, adjt = ops.stack_fwd_planes(
+        b.x, g, Ws, [torch.zeros(D, device=dev)] * (L + 1), keep_planes=True)
     adjt_ptr = adjt.data_ptr() if adjt is not None else ops._adjt_ptr(planes_t, L)
     lib = _lib.load()
     P = lib.lgnn_gcn_stack_bwd_partials(M)

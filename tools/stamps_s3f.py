@@ -63,9 +63,8 @@ def run():
     dlog = torch.randn(b.num_graphs, 5, device=dev, generator=gen)
     dS_ws = torch.empty(2 * M * 128, device=dev)
     # the forward's Â^T planes handed to the backward (STAMPS_ADJT=0: rebuilt from the CSR)
-    keep = {}
-    ops.stack_fwd(b.x, g, Ws, [torch.zeros(D, device=dev)] * (L + 1), keep)
-    planes_t = keep["planes_t"]
+    planes_t = ops.stack_fwd_planes(b.x, g, Ws, [torch.zeros(D, device=dev)] * (L + 1),
+                                    keep_planes=True, adjt_after_planes=True)[2]
     adjt_ptr = ops._adjt_ptr(planes_t, L) if os.environ.get("STAMPS_ADJT", "1") != "0" else None
     s = torch.cuda.current_stream().cuda_stream
     arr = ctypes.c_void_p * (L + 1)
