@@ -107,7 +107,7 @@ int lgnn_get_option(int option);
  * order: PyG knn_graph groups the edges by target) the third launch writes the CSR by a scan of
  * the row lengths and a coalesced copy, and the count / fill / finish launches return at once;
  * otherwise the general counting-sort launches run. Same outputs either way (bit-identical).
- * LGNN_GRAPH_SORTED=0 in the environment disables the fast path (A/B, tests).
+ * lgnn_set_option(LGNN_OPT_GRAPH_SORTED, 0) disables the fast path (A/B, tests).
  * ------------------------------------------------------------------------------------------- */
 size_t lgnn_graph_workspace_bytes(int64_t num_nodes, int64_t num_edges);
 int lgnn_graph_build(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes, int loops,

@@ -177,11 +177,10 @@ def dropout_masks_raw(state: torch.Tensor, numels: list, thr: int, scale: float)
         tot += _pad4(int(n))
     flat = torch.empty(tot, dtype=torch.float32, device=dev)
     k = len(numels)
-    base = flat.data_ptr()
-    _lib.call("lgnn_dropout_masks", k, (ctypes.c_void_p * k)(*[base + 4 * o for o in offs]),
-              (ctypes.c_int64 * k)(*[int(n) for n in numels]),
+    # thr / scale: host arrays of uint32 / float, which marshalling has no list form for
+    _lib.call("lgnn_dropout_masks", k, [flat[o:] for o in offs], [int(n) for n in numels],
               (ctypes.c_uint32 * k)(*([thr] * k)), (ctypes.c_float * k)(*([scale] * k)),
-              state.data_ptr(), 1, _lib.stream(dev))
+              state, 1, _lib.stream(dev))
     return flat
 
 
@@ -191,8 +190,7 @@ def _mul(x: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
         raise _lib.LgnnError("mask_mul: fp32 tensors of one shape")
     x, m = x.contiguous(), m.contiguous()
     y = torch.empty_like(x)
-    _lib.call("lgnn_mask_mul", _lib.ptr(x), _lib.ptr(m), _lib.ptr(y), x.numel(),
-              _lib.stream(x.device))
+    _lib.call("lgnn_mask_mul", x, m, y, x.numel(), _lib.stream(x.device))
     return y
 
 

@@ -43,6 +43,9 @@ class Csr:
     err: torch.Tensor     # int32 [1] count of dropped out-of-range edges
 
 
+NO_CSR = Csr(*(None,) * 9)  # every array NULL: `csr or NO_CSR` where a launch's CSR is optional
+
+
 class Graph:
     """edge_index [2, E] int64 (source, target) + sorted `batch` [N] -> device CSR views."""
 
@@ -88,8 +91,8 @@ class Graph:
             self._gptr = torch.ops.lgnn.batch_ptr(self.batch, self.num_graphs)
         if self._gptr is None and self.batch is not None:
             self._gptr = torch.empty(self.num_graphs + 1, dtype=torch.int32, device=self.device)
-            _lib.call("lgnn_batch_ptr", _lib.ptr(self.batch), self.num_nodes, self.num_graphs,
-                      _lib.ptr(self._gptr), _lib.stream(self.device))
+            _lib.call("lgnn_batch_ptr", self.batch, self.num_nodes, self.num_graphs, self._gptr,
+                      _lib.stream(self.device))
         return self._gptr
 
     def csr(self, kind: str) -> Csr:
@@ -136,12 +139,9 @@ class Graph:
         gptr = None  # the graph offsets ride along with the first build
         if self._gptr is None and self.batch is not None:
             gptr = self._gptr = torch.empty(self.num_graphs + 1, dtype=torch.int32, device=dev)
-        args = (_lib.ptr(self.edge_index), e, n, loops, norm,
-                _lib.ptr(c.rowptr), _lib.ptr(c.col), _lib.ptr(c.w), _lib.ptr(c.tptr),
-                _lib.ptr(c.tidx), _lib.ptr(c.tw), _lib.ptr(c.tmap), _lib.ptr(c.tile_open),
-                _lib.ptr(self.batch) if gptr is not None else None,
-                self.num_graphs if gptr is not None else 0, _lib.ptr(gptr), _lib.ptr(c.err),
-                _lib.ptr(ws), ws_bytes)
+        args = (self.edge_index, e, n, loops, norm, c.rowptr, c.col, c.w, c.tptr, c.tidx, c.tw,
+                c.tmap, c.tile_open, self.batch if gptr is not None else None,
+                self.num_graphs if gptr is not None else 0, gptr, c.err, ws, ws_bytes)
         if planes is not None:
             _lib.call("lgnn_graph_build_planes", *args, int(kind == "gcn_lazy"),
                       ctypes.byref(planes), _lib.stream(dev))
@@ -163,8 +163,8 @@ class Graph:
         if k != kind:
             raise ValueError(f"no eager build of {kind!r} on this graph kept its workspace "
                              "(set Graph.keep_build_workspace = True, or KEEP_BUILD_WS = True)")
-        r = _lib.load().lgnn_graph_build_path(_lib.ptr(ws), self.num_nodes, self.num_edges,
-                                              _lib.stream(self.device))
+        r = _lib.query("lgnn_graph_build_path", ws, self.num_nodes, self.num_edges,
+                       _lib.stream(self.device))
         _lib.check(r if r < 0 else 0, "lgnn_graph_build_path")
         return {1: "sorted", 2: "sorted_open"}.get(r, "general")
 
@@ -219,8 +219,8 @@ class Graph:
             n_t = _lib.load().lgnn_tile_count(self.num_nodes)
             t = torch.empty(n_t + _lib.LGNN_TILE_OPEN_EXTRA, dtype=torch.int32,
                             device=self.device)
-            _lib.call("lgnn_tile_open", _lib.ptr(c.rowptr), _lib.ptr(c.col), self.num_nodes,
-                      _lib.ptr(t), _lib.stream(self.device))
+            _lib.call("lgnn_tile_open", c.rowptr, c.col, self.num_nodes, t,
+                      _lib.stream(self.device))
             self._aux[key] = t
         return self._aux[key]
 

@@ -51,16 +51,15 @@ def knn_graph(pos: torch.Tensor, k: int, batch: torch.Tensor | None = None, loop
         num_graphs = int(batch.max().item()) + 1 if N > 0 else 0
     B = int(num_graphs)
     ptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    _lib.call("lgnn_batch_ptr", _lib.ptr(batch), N, B, _lib.ptr(ptr), _lib.stream(dev))
+    _lib.call("lgnn_batch_ptr", batch, N, B, ptr, _lib.stream(dev))
     n = (ptr[1:] - ptr[:-1]).to(torch.int64)
     kk = torch.clamp(n, max=k) if loop else torch.clamp(torch.clamp(n, max=k + 1) - 1, min=0)
     E = int((n * kk).sum().item()) if B > 0 else 0  # one host sync: sizes the output
     out = torch.empty(2, E, dtype=torch.int64, device=dev)
     ws = torch.empty(max(1, _lib.load().lgnn_knn_workspace_bytes(B)), dtype=torch.uint8,
                      device=dev)
-    _lib.call("lgnn_knn_graph", _lib.ptr(pos), N, pos.size(1), _lib.ptr(batch), _lib.ptr(ptr), B,
-              int(k), int(bool(loop)), _lib.ptr(out), E, _lib.ptr(ws), ws.numel(),
-              _lib.stream(dev))
+    _lib.call("lgnn_knn_graph", pos, N, pos.size(1), batch, ptr, B, int(k), int(bool(loop)), out,
+              E, ws, ws.numel(), _lib.stream(dev))
     if flow == "target_to_source":
         out = out.flip(0)
     return out
@@ -77,7 +76,7 @@ def _batch_ptr(pos, batch, num_graphs):
         num_graphs = int(batch.max().item()) + 1 if N > 0 else 0
     B = int(num_graphs)
     ptr = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    _lib.call("lgnn_batch_ptr", _lib.ptr(batch), N, B, _lib.ptr(ptr), _lib.stream(dev))
+    _lib.call("lgnn_batch_ptr", batch, N, B, ptr, _lib.stream(dev))
     return batch, ptr, B
 
 
@@ -103,13 +102,11 @@ def radius_graph(pos: torch.Tensor, r: float, batch: torch.Tensor | None = None,
     batch, ptr, B = _batch_ptr(pos, batch, num_graphs)
     lib = _lib.load()
     ws = torch.empty(max(1, lib.lgnn_radius_workspace_bytes(N)), dtype=torch.uint8, device=dev)
-    args = (_lib.ptr(pos), N, pos.size(1), _lib.ptr(batch), _lib.ptr(ptr), B, float(r),
-            int(max_num_neighbors), int(bool(loop)))
-    _lib.call("lgnn_radius_count", *args, _lib.ptr(ws), ws.numel(), _lib.stream(dev))
+    args = (pos, N, pos.size(1), batch, ptr, B, float(r), int(max_num_neighbors), int(bool(loop)))
+    _lib.call("lgnn_radius_count", *args, ws, ws.numel(), _lib.stream(dev))
     E = int(ws[8 * N:8 * N + 8].view(torch.int64).item())  # one host sync: sizes the output
     out = torch.empty(2, E, dtype=torch.int64, device=dev)
-    _lib.call("lgnn_radius_graph", *args, _lib.ptr(out), E, _lib.ptr(ws), ws.numel(),
-              _lib.stream(dev))
+    _lib.call("lgnn_radius_graph", *args, out, E, ws, ws.numel(), _lib.stream(dev))
     if flow == "target_to_source":
         out = out.flip(0)
     return out

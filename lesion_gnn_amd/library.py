@@ -153,7 +153,7 @@ def batch_ptr(batch: Tensor, num_graphs: int) -> Tensor:
     from . import _lib
 
     gptr = torch.empty(num_graphs + 1, dtype=torch.int32, device=batch.device)
-    _lib.call("lgnn_batch_ptr", _lib.ptr(batch), batch.numel(), num_graphs, _lib.ptr(gptr),
+    _lib.call("lgnn_batch_ptr", batch, batch.numel(), num_graphs, gptr,
               _lib.stream(batch.device))
     return gptr
 

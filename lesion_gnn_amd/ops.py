@@ -19,7 +19,7 @@ import torch
 from torch.utils import _pytree as pytree
 
 from . import _lib
-from .graph import Csr, Graph
+from .graph import NO_CSR, Csr, Graph
 
 
 def _compiling() -> bool:
@@ -76,15 +76,14 @@ def linear_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, act: in
         Wp = dense_planes(W, False, False)
         y = torch.empty(M, N, dtype=torch.float32, device=x.device)
         for r0, r1 in _row_blocks(M, K, N):
-            _lib.call("lgnn_s3_gemm_act", _lib.ptr(S) + r0 * K * 4, r1 - r0, K, _lib.ptr(Wp), N,
-                      _lib.ptr(b), act, _lib.ptr(y) + r0 * N * 4, _s(x.device))
+            _lib.call("lgnn_s3_gemm_act", _lib.ptr(S) + r0 * K * 4, r1 - r0, K, Wp, N, b, act,
+                      _lib.ptr(y) + r0 * N * 4, _s(x.device))
         return (y, S) if save_s else y
     y = torch.empty(M, N, dtype=torch.float32, device=x.device)
     s_out = torch.empty(M, K, dtype=torch.float32, device=x.device) if save_s else None
-    _lib.call("lgnn_node_linear_fwd", _lib.ptr(x), M, K,
-              _lib.ptr(csr.rowptr) if csr else None, _lib.ptr(csr.col) if csr else None,
-              _lib.ptr(csr.w) if csr else None, float(self_scale), _lib.ptr(W), _lib.ptr(b), N,
-              act, _lib.ptr(y), _lib.ptr(s_out), _s(x.device))
+    c = csr or NO_CSR
+    _lib.call("lgnn_node_linear_fwd", x, M, K, c.rowptr, c.col, c.w, float(self_scale), W, b, N,
+              act, y, s_out, _s(x.device))
     return (y, s_out) if save_s else y
 
 
@@ -208,10 +207,8 @@ def plane_job(Ws: list, d_in: int, planes, planes_t) -> _lib.PlaneJob:
 
 def run_plane_job(job: _lib.PlaneJob, dev) -> None:
     """The split of `job` as its own launch (lgnn_weight_planes)."""
-    arr = ctypes.c_void_p * job.nl
-    _lib.call("lgnn_weight_planes", job.nl, arr(*[job.W[i] for i in range(job.nl)]),
-              (ctypes.c_int * (job.nl + 1))(*[job.widths[i] for i in range(job.nl + 1)]),
-              job.planes, job.planes_t, _s(dev))
+    _lib.call("lgnn_weight_planes", job.nl, job.W[:job.nl], job.widths[:job.nl + 1], job.planes,
+              job.planes_t, _s(dev))
 
 
 def weight_planes(Ws: list, d_in: int, transposed: bool = False, extra: int = 0):
@@ -293,42 +290,32 @@ def stack_fwd_planes(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: st
         else:
             adjt_t = torch.empty(adjt_numel(M), dtype=torch.int16, device=dev) \
                 if want_adjt else None
-            adjt = _lib.ptr(adjt_t)
+            adjt = adjt_t
     else:
         csr = graph.csr(kind)
         planes_t = adjt_t = None
     open_ = graph.tile_open(kind)
     hs = [torch.empty(M, W.size(0), dtype=torch.float32, device=dev) for W in Ws]
     ss = [torch.empty(M, Ws[l].size(1), dtype=torch.float32, device=dev) for l in range(1, L + 1)]
-    arr = ctypes.c_void_p * (L + 1)
-    Wp = arr(*[W.data_ptr() for W in Ws])
-    bp = arr(*[b.data_ptr() for b in bs])
-    Hp = arr(*[h.data_ptr() for h in hs])
-    widths = (ctypes.c_int * (L + 1))(*[W.size(0) for W in Ws])
+    widths = [W.size(0) for W in Ws]
     if s3:
         if _open_in_fused(OPEN_IN_FUSED, graph, "fwd"):  # open tiles in the same launch
-            _lib.call("lgnn_gcn_stack_fwd_s3_all", _lib.ptr(x), M, x.size(1), 1,
-                      _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(csr.w), L,
-                      _lib.ptr(planes), Wp, bp, widths, Hp,
-                      (ctypes.c_void_p * L)(*[t.data_ptr() for t in ss]), _lib.ptr(open_),
-                      adjt, _s(dev))
+            _lib.call("lgnn_gcn_stack_fwd_s3_all", x, M, x.size(1), 1, csr.rowptr, csr.col,
+                      csr.w, L, planes, Ws, bs, widths, hs, ss, open_, adjt, _s(dev))
             return hs, ss, planes_t, adjt_t
-        _lib.call("lgnn_gcn_stack_fwd_s3", _lib.ptr(x), M, x.size(1), 1, _lib.ptr(csr.rowptr),
-                  _lib.ptr(csr.col), _lib.ptr(csr.w), L, _lib.ptr(planes), bp, widths, Hp,
-                  _lib.ptr(open_), adjt, _s(dev))
+        _lib.call("lgnn_gcn_stack_fwd_s3", x, M, x.size(1), 1, csr.rowptr, csr.col, csr.w, L,
+                  planes, bs, widths, hs, open_, adjt, _s(dev))
     else:
-        _lib.call("lgnn_gcn_stack_fwd", _lib.ptr(x), M, x.size(1), 1, _lib.ptr(csr.rowptr),
-                  _lib.ptr(csr.col), _lib.ptr(csr.w), L, Wp, bp, widths, Hp, _lib.ptr(open_),
-                  _s(dev))
+        _lib.call("lgnn_gcn_stack_fwd", x, M, x.size(1), 1, csr.rowptr, csr.col, csr.w, L, Ws,
+                  bs, widths, hs, open_, _s(dev))
     for l in range(L + 1):
         inp = x if l == 0 else hs[l - 1]
-        c = csr if l > 0 else None
+        c = csr if l > 0 else NO_CSR
         s_out = ss[l - 1] if l > 0 else None
-        _lib.call("lgnn_node_linear_fwd_tiles", _lib.ptr(inp), M, inp.size(1),
-                  _lib.ptr(c.rowptr) if c else None, _lib.ptr(c.col) if c else None,
-                  _lib.ptr(c.w) if c else None, 0.0, _lib.ptr(Ws[l]), _lib.ptr(bs[l]),
-                  Ws[l].size(0), _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE,
-                  _lib.ptr(hs[l]), _lib.ptr(s_out), _lib.ptr(open_), 1, _s(dev))
+        _lib.call("lgnn_node_linear_fwd_tiles", inp, M, inp.size(1), c.rowptr, c.col, c.w, 0.0,
+                  Ws[l], bs[l], Ws[l].size(0),
+                  _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE, hs[l], s_out, open_, 1,
+                  _s(dev))
     return hs, ss, planes_t, adjt_t
 
 
@@ -358,7 +345,7 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
     s3f = s3 and _s3f(L) and (L <= 2 or _open_in_fused(OPEN_IN_FUSED_BWD, graph, "bwd"))
     # the forward's Â^T tiles: their own buffer (adjt_t), or room after the planes (weight_planes'
     # `extra`); none -> the backward rebuilds them from the CSR
-    adjt = (_lib.ptr(adjt_t) if adjt_t is not None else _adjt_ptr(planes_t, L)) if s3f else None
+    adjt = (adjt_t if adjt_t is not None else _adjt_ptr(planes_t, L)) if s3f else None
     P = lib.lgnn_gcn_stack_bwd_s3_partials(M) if s3 and not s3f else \
         lib.lgnn_gcn_stack_bwd_partials(M)
     _lib.check(0 if P > 0 else P, "lgnn_gcn_stack_bwd_partials")
@@ -371,7 +358,6 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
         dWp.append(slab[off:off + P * nk])
         dbp.append(slab[off + P * nk:off + P * (nk + n)])
         off += P * (nk + n)
-    arr = ctypes.c_void_p * (L + 1)
     Sx = [x] + list(ss)
     dlog, W_out = head if head is not None else (None, None)
     ce = dlog if isinstance(dlog, _lib.CeSrc) else None  # CE-formed logits gradient
@@ -379,19 +365,15 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
     if s3f and _open_in_fused(OPEN_IN_FUSED_BWD, graph, "bwd"):  # one launch, open tiles last
         # L = 3: the third [M][128] block receives dZ_0, the in_proj output gradient
         dS_ws = torch.empty((3 if L == 3 else 2) * M * 128, dtype=torch.float32, device=dev)
-        common = (_lib.ptr(graph.batch), _lib.ptr(graph.gptr), int(mean), B,
-                  _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(csr.w), _lib.ptr(csr.tptr),
-                  _lib.ptr(csr.tidx), _lib.ptr(csr.tw), _lib.ptr(x), M, L, _lib.ptr(planes_t),
-                  arr(*[W.data_ptr() for W in Ws]), arr(*[h.data_ptr() for h in hs]),
-                  (ctypes.c_void_p * L)(*[t.data_ptr() for t in ss]),
-                  (ctypes.c_int * (L + 2))(*widths), arr(*[t.data_ptr() for t in dWp]),
-                  arr(*[t.data_ptr() for t in dbp]), P, _lib.ptr(dS_ws), _lib.ptr(open_))
+        common = (graph.batch, graph.gptr, int(mean), B, csr.rowptr, csr.col, csr.w, csr.tptr,
+                  csr.tidx, csr.tw, x, M, L, planes_t, Ws, hs, ss, widths, dWp, dbp, P, dS_ws,
+                  open_)
         if ce is not None:
-            _lib.call("lgnn_gcn_stack_bwd_s3f_ce", *common, ctypes.byref(ce), _lib.ptr(W_out),
+            _lib.call("lgnn_gcn_stack_bwd_s3f_ce", *common, ctypes.byref(ce), W_out,
                       W_out.size(0), adjt, _s(dev))
         else:
-            _lib.call("lgnn_gcn_stack_bwd_s3f_all", _lib.ptr(dp), *common, _lib.ptr(dlog),
-                      _lib.ptr(W_out), W_out.size(0) if head else 0, adjt, _s(dev))
+            _lib.call("lgnn_gcn_stack_bwd_s3f_all", dp, *common, dlog, W_out,
+                      W_out.size(0) if head else 0, adjt, _s(dev))
         if L == 3:  # in_proj: (dW_0, db_0) = (dZ_0^T X, colsum dZ_0), one split-3 GEMM
             dz0 = dS_ws[2 * M * 128:2 * M * 128 + M * widths[1]].view(M, widths[1])
             first = dense_wgrad(dz0, x, False, want_db=True, reducer=reducer)
@@ -399,42 +381,30 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
         return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer)
     assert head is None, "dP from the logits gradient only in the single-launch split-3 path"
     if s3f:  # one fused split-3 launch, every layer of a tile in one pass (stack3_bwd.hip)
-        _lib.call("lgnn_gcn_stack_bwd_s3f", _lib.ptr(dp), _lib.ptr(graph.batch),
-                  _lib.ptr(graph.gptr), int(mean), dp.size(0), _lib.ptr(csr.rowptr),
-                  _lib.ptr(csr.col), _lib.ptr(csr.w), _lib.ptr(x), M, L, _lib.ptr(planes_t),
-                  arr(*[h.data_ptr() for h in hs]), (ctypes.c_int * (L + 2))(*widths),
-                  arr(*[t.data_ptr() for t in dWp]), arr(*[t.data_ptr() for t in dbp]), P,
-                  _lib.ptr(open_), adjt, _s(dev))
+        _lib.call("lgnn_gcn_stack_bwd_s3f", dp, graph.batch, graph.gptr, int(mean), dp.size(0),
+                  csr.rowptr, csr.col, csr.w, x, M, L, planes_t, hs, widths, dWp, dbp, P, open_,
+                  adjt, _s(dev))
     elif s3:  # one split-3 launch per layer (stack3_bwd.hip); dZ between them in dz_ws
         dz_ws = torch.empty(2 * M * 128, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_gcn_stack_bwd_s3", _lib.ptr(dp), _lib.ptr(graph.batch),
-                  _lib.ptr(graph.gptr), int(mean), dp.size(0), _lib.ptr(csr.rowptr),
-                  _lib.ptr(csr.col), _lib.ptr(csr.w), _lib.ptr(x), M, L, _lib.ptr(planes_t),
-                  arr(*[h.data_ptr() for h in hs]), (ctypes.c_int * (L + 2))(*widths),
-                  arr(*[t.data_ptr() for t in dWp]), arr(*[t.data_ptr() for t in dbp]), P,
-                  _lib.ptr(dz_ws), _lib.ptr(open_), _s(dev))
+        _lib.call("lgnn_gcn_stack_bwd_s3", dp, graph.batch, graph.gptr, int(mean), dp.size(0),
+                  csr.rowptr, csr.col, csr.w, x, M, L, planes_t, hs, widths, dWp, dbp, P, dz_ws,
+                  open_, _s(dev))
     else:
-        _lib.call("lgnn_gcn_stack_bwd", _lib.ptr(dp), _lib.ptr(graph.batch),
-                  _lib.ptr(graph.gptr), int(mean), _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
-                  _lib.ptr(csr.w), _lib.ptr(x), M, L, arr(*[W.data_ptr() for W in Ws]),
-                  arr(*[h.data_ptr() for h in hs]), (ctypes.c_int * (L + 2))(*widths),
-                  arr(*[t.data_ptr() for t in dWp]), arr(*[t.data_ptr() for t in dbp]), P,
-                  _lib.ptr(open_), _s(dev))
+        _lib.call("lgnn_gcn_stack_bwd", dp, graph.batch, graph.gptr, int(mean), csr.rowptr,
+                  csr.col, csr.w, x, M, L, Ws, hs, widths, dWp, dbp, P, open_, _s(dev))
     dS = None
     for l in reversed(range(L + 1)):
         K, N = widths[l], widths[l + 1]
         if l == L:
-            mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, None
+            mode, dY, tc = _lib.LGNN_GRAD_POOL, dp, NO_CSR
         else:
             mode, dY, tc = _lib.LGNN_GRAD_TRANSPOSE, dS, csr
         dX = torch.empty(M, K, dtype=torch.float32, device=dev) if l > 0 else None
-        _lib.call("lgnn_node_linear_bwd_tiles", mode, _lib.ptr(dY), _lib.ptr(graph.batch),
-                  _lib.ptr(graph.gptr), int(mean), _lib.ptr(tc.tptr) if tc else None,
-                  _lib.ptr(tc.tidx) if tc else None, _lib.ptr(tc.tw) if tc else None, 0.0,
-                  _lib.ptr(hs[l]) if l > 0 else None,
-                  _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE, _lib.ptr(Sx[l]), M, K,
-                  None, None, None, 0.0, _lib.ptr(Ws[l]), N, _lib.ptr(dX), _lib.ptr(dWp[l]),
-                  _lib.ptr(dbp[l]), P, _lib.ptr(open_), 1, 2 if s3f else 1, _s(dev))
+        _lib.call("lgnn_node_linear_bwd_tiles", mode, dY, graph.batch, graph.gptr, int(mean),
+                  tc.tptr, tc.tidx, tc.tw, 0.0, hs[l] if l > 0 else None,
+                  _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE, Sx[l], M, K, None, None,
+                  None, 0.0, Ws[l], N, dX, dWp[l], dbp[l], P, open_, 1, 2 if s3f else 1,
+                  _s(dev))
         dS = dX
     return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer)
 
@@ -477,8 +447,7 @@ def linear_bwd(grad_mode: int, dY: torch.Tensor, *, H: torch.Tensor | None, act:
             g = _f32c(dY)
         if act == _lib.LGNN_ACT_ELU:
             dZ = torch.empty_like(g)
-            _lib.call("lgnn_act_bwd", _lib.ptr(g), _lib.ptr(H), _lib.ptr(dZ), g.numel(), act,
-                      _s(dev))
+            _lib.call("lgnn_act_bwd", g, H, dZ, g.numel(), act, _s(dev))
         else:
             dZ = g
         S = spmm_raw(csr.rowptr, csr.col, csr.w, self_scale, X) if csr is not None else X
@@ -492,13 +461,10 @@ def linear_bwd(grad_mode: int, dY: torch.Tensor, *, H: torch.Tensor | None, act:
     dX = torch.empty(M, K, dtype=torch.float32, device=dev) if want_dx else None
     batch = graph.batch if graph is not None else None
     gptr = graph.gptr if graph is not None else None
-    _lib.call(
-        "lgnn_node_linear_bwd", grad_mode, _lib.ptr(dY), _lib.ptr(batch), _lib.ptr(gptr),
-        int(pool_mean), _lib.ptr(tcsr.tptr) if tcsr else None,
-        _lib.ptr(tcsr.tidx) if tcsr else None, _lib.ptr(tcsr.tw) if tcsr else None, float(tself),
-        _lib.ptr(H), act, _lib.ptr(X), M, K, _lib.ptr(csr.rowptr) if csr else None,
-        _lib.ptr(csr.col) if csr else None, _lib.ptr(csr.w) if csr else None, float(self_scale),
-        _lib.ptr(W), N, _lib.ptr(dX), _lib.ptr(dWp), _lib.ptr(dbp), P, _s(dev))
+    t, c = tcsr or NO_CSR, csr or NO_CSR
+    _lib.call("lgnn_node_linear_bwd", grad_mode, dY, batch, gptr, int(pool_mean), t.tptr, t.tidx,
+              t.tw, float(tself), H, act, X, M, K, c.rowptr, c.col, c.w, float(self_scale), W, N,
+              dX, dWp, dbp, P, _s(dev))
     dW = torch.empty(N, K, dtype=torch.float32, device=dev)
     db = torch.empty(N, dtype=torch.float32, device=dev) if want_db else None
     jobs = [(dWp, P, N * K, dW)] + ([(dbp, P, N, db)] if want_db else [])
@@ -521,19 +487,17 @@ def reduce_multi(jobs: list, dev, ce=None, num_classes: int = 0) -> None:
         chunk = jobs[i:i + 16]
         n = len(chunk)
         is_ce = [j[0] is CE_PART for j in chunk]
-        parts = (ctypes.c_void_p * n)(*[None if c else j[0].data_ptr()
-                                        for j, c in zip(chunk, is_ce)])
-        nps = (ctypes.c_int * n)(*[j[1] for j in chunk])
-        lens = (ctypes.c_int64 * n)(*[j[2] for j in chunk])
-        outs = (ctypes.c_void_p * n)(*[j[3].data_ptr() for j in chunk])
-        fac = (ctypes.c_void_p * n)(*[j[4].data_ptr() if len(j) > 4 else None for j in chunk])
-        wid = (ctypes.c_int * n)(*[j[5] if len(j) > 4 else 0 for j in chunk])
+        parts = [None if c else j[0] for j, c in zip(chunk, is_ce)]
+        nps = [j[1] for j in chunk]
+        lens = [j[2] for j in chunk]
+        outs = [j[3] for j in chunk]
+        fac = [j[4] if len(j) > 4 else None for j in chunk]
+        wid = [j[5] if len(j) > 4 else 0 for j in chunk]
         if any(is_ce):
             if ce is None:
                 raise _lib.LgnnError("reduce_multi: a CE_PART job needs the CE source")
             _lib.call("lgnn_reduce_jobs_ce", n, parts, fac, wid, nps, lens, outs,
-                      (ctypes.c_int * n)(*[int(c) for c in is_ce]), ctypes.byref(ce),
-                      int(num_classes), _s(dev))
+                      [int(c) for c in is_ce], ctypes.byref(ce), int(num_classes), _s(dev))
         elif any(len(j) > 4 for j in chunk):
             _lib.call("lgnn_reduce_jobs", n, parts, fac, wid, nps, lens, outs, _s(dev))
         else:
@@ -543,8 +507,7 @@ def reduce_multi(jobs: list, dev, ce=None, num_classes: int = 0) -> None:
 def spmm_raw(rowptr, col, w, self_scale: float, x: torch.Tensor) -> torch.Tensor:
     M, D = x.shape
     y = torch.empty_like(x)
-    _lib.call("lgnn_spmm", _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(w), float(self_scale),
-              _lib.ptr(x), M, D, _lib.ptr(y), _s(x.device))
+    _lib.call("lgnn_spmm", rowptr, col, w, float(self_scale), x, M, D, y, _s(x.device))
     return y
 
 
@@ -553,8 +516,7 @@ def pool_head_fwd(H: torch.Tensor, graph: Graph, mean: bool, Wout=None, bout=Non
     pooled = torch.empty(B, D, dtype=torch.float32, device=H.device)
     C = Wout.size(0) if Wout is not None else 0
     logits = torch.empty(B, C, dtype=torch.float32, device=H.device) if Wout is not None else None
-    _lib.call("lgnn_pool_head_fwd", _lib.ptr(H), _lib.ptr(graph.gptr), B, D, int(mean),
-              _lib.ptr(Wout), _lib.ptr(bout), C, _lib.ptr(pooled), _lib.ptr(logits),
+    _lib.call("lgnn_pool_head_fwd", H, graph.gptr, B, D, int(mean), Wout, bout, C, pooled, logits,
               _s(H.device))
     return pooled, logits
 
@@ -566,16 +528,15 @@ def pool_head_bwd(dlogits: torch.Tensor, pooled: torch.Tensor, Wout: torch.Tenso
     dp = torch.empty(B, D, dtype=torch.float32, device=dev)
     dWo = torch.empty(C, D, dtype=torch.float32, device=dev)
     dbo = torch.empty(C, dtype=torch.float32, device=dev)
-    _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D, _lib.ptr(Wout), C,
-              _lib.ptr(dp), _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
+    _lib.call("lgnn_pool_head_bwd", dlogits, pooled, B, D, Wout, C, dp, dWo, dbo, _s(dev))
     return dp, dWo, dbo
 
 
 def pool_bwd(dpooled: torch.Tensor, graph: Graph, mean: bool, M: int) -> torch.Tensor:
     D = dpooled.size(1)
     dH = torch.empty(M, D, dtype=torch.float32, device=dpooled.device)
-    _lib.call("lgnn_pool_bwd", _lib.ptr(dpooled), _lib.ptr(graph.batch), _lib.ptr(graph.gptr), M,
-              D, int(mean), _lib.ptr(dH), _s(dpooled.device))
+    _lib.call("lgnn_pool_bwd", dpooled, graph.batch, graph.gptr, M, D, int(mean), dH,
+              _s(dpooled.device))
     return dH
 
 
@@ -666,8 +627,7 @@ def dense_planes(W: torch.Tensor, transposed: bool, bf16: bool) -> torch.Tensor:
     planes = 1 if bf16 else 3
     n = _lib.load().lgnn_s3_weight_planes_numel(out, inn, planes)
     Wp = torch.empty(n, dtype=torch.int16, device=W.device)
-    _lib.call("lgnn_s3_weight_planes", _lib.ptr(W), rows, cols, int(transposed), planes,
-              _lib.ptr(Wp), _s(W.device))
+    _lib.call("lgnn_s3_weight_planes", W, rows, cols, int(transposed), planes, Wp, _s(W.device))
     return Wp
 
 
@@ -691,13 +651,10 @@ def s3_bundle_raw(Ws: list, transposed: list, bf16: bool) -> torch.Tensor:
     views = flat.split(sizes)
     for j0 in range(0, len(Ws), 16):
         js = range(j0, min(j0 + 16, len(Ws)))
-        n = len(js)
-        P_ = ctypes.c_void_p * n
-        I_ = ctypes.c_int * n
-        _lib.call("lgnn_s3_weight_planes_multi", n, P_(*[Ws[j].data_ptr() for j in js]),
-                  I_(*[Ws[j].size(0) for j in js]), I_(*[Ws[j].size(1) for j in js]),
-                  I_(*[int(bool(transposed[j])) for j in js]), 1 if bf16 else 3,
-                  P_(*[views[j].data_ptr() for j in js]), _s(flat.device))
+        _lib.call("lgnn_s3_weight_planes_multi", len(js), [Ws[j] for j in js],
+                  [Ws[j].size(0) for j in js], [Ws[j].size(1) for j in js],
+                  [int(bool(transposed[j])) for j in js], 1 if bf16 else 3,
+                  [views[j] for j in js], _s(flat.device))
     return flat
 
 
@@ -738,10 +695,10 @@ def dense_mm(a: torch.Tensor, Wp: torch.Tensor, N: int, bias, bf16: bool,
     Y = torch.empty(M, N, dtype=torch.float32, device=a.device)
     cs = torch.empty((M + 63) // 64 * N, dtype=torch.float32, device=a.device) \
         if want_colsum and M > 0 else None
-    bp = _lib.ptr(_f32c(bias) if bias is not None else None)
+    bias = _f32c(bias) if bias is not None else None
     for r0, r1 in _row_blocks(M, K, N):
-        _lib.call("lgnn_s3_gemm", _lib.ptr(a) + r0 * K * 4, r1 - r0, K, _lib.ptr(Wp), N,
-                  1 if bf16 else 3, bp, _lib.ptr(Y) + r0 * N * 4,
+        _lib.call("lgnn_s3_gemm", _lib.ptr(a) + r0 * K * 4, r1 - r0, K, Wp, N,
+                  1 if bf16 else 3, bias, _lib.ptr(Y) + r0 * N * 4,
                   _lib.ptr(cs) + (r0 // 64) * N * 4 if cs is not None else None, _s(a.device))
     if cs is not None:
         _COLSUMS[id(Y)] = (weakref.ref(Y), Y._version, cs)
@@ -817,14 +774,9 @@ def bf16_prepare_weights(weights: list) -> None:
         WTb = torch.empty(128 * lib.lgnn_bf16_kpad(N), dtype=torch.bfloat16, device=W.device) \
             if K <= 128 else None
         ops_.append((W, Wb, WTb))
-    n = len(ops_)
-    P_ = ctypes.c_void_p * n
-    I_ = ctypes.c_int * n
-    _lib.call("lgnn_bf16_weight_prep_multi", n, P_(*[o[0].data_ptr() for o in ops_]),
-              I_(*[o[0].size(0) for o in ops_]), I_(*[o[0].size(1) for o in ops_]),
-              P_(*[o[1].data_ptr() for o in ops_]),
-              P_(*[o[2].data_ptr() if o[2] is not None else None for o in ops_]),
-              _s(ws[0].device))
+    _lib.call("lgnn_bf16_weight_prep_multi", len(ops_), [o[0] for o in ops_],
+              [o[0].size(0) for o in ops_], [o[0].size(1) for o in ops_],
+              [o[1] for o in ops_], [o[2] for o in ops_], _s(ws[0].device))
     for W, Wb, WTb in ops_:
         _PREPARED[id(W)] = (weakref.ref(W), W._version, Wb, WTb)
 
@@ -843,8 +795,7 @@ def bf16_weight_operands(W: torch.Tensor, want_t: bool):
     Wb = torch.empty(128 * lib.lgnn_bf16_kpad(K), dtype=torch.bfloat16, device=W.device)
     WTb = torch.empty(128 * lib.lgnn_bf16_kpad(N), dtype=torch.bfloat16, device=W.device) \
         if want_t and K <= 128 else None
-    _lib.call("lgnn_bf16_weight_prep", _lib.ptr(W), N, K, _lib.ptr(Wb), _lib.ptr(WTb),
-              _s(W.device))
+    _lib.call("lgnn_bf16_weight_prep", W, N, K, Wb, WTb, _s(W.device))
     return Wb, WTb
 
 
@@ -860,10 +811,10 @@ def bf16_gemm(A: torch.Tensor, Wb: torch.Tensor, bias, N: int, want_yb: bool = F
     cs = torch.empty((M + 63) // 64 * N, dtype=torch.float32, device=A.device) \
         if want_colsum and M > 0 else None
     es = A.element_size()
-    bp = _lib.ptr(_f32c(bias) if bias is not None else None)
+    bias = _f32c(bias) if bias is not None else None
     for r0, r1 in _row_blocks(M, K, N):  # row blocks past the kernel's 32-bit offsets
         _lib.call("lgnn_bf16_gemm", _lib.ptr(A) + r0 * K * es, int(A.dtype == torch.float32),
-                  r1 - r0, K, _lib.ptr(Wb), bp, N, _lib.ptr(Y) + r0 * N * 4,
+                  r1 - r0, K, Wb, bias, N, _lib.ptr(Y) + r0 * N * 4,
                   _lib.ptr(Yb) + r0 * N * 2 if Yb is not None else None,
                   _lib.ptr(cs) + (r0 // 64) * N * 4 if cs is not None else None, _s(A.device))
     if cs is not None:
@@ -890,8 +841,7 @@ def colsum_of(y: torch.Tensor, reducer: list = None):
     if reducer is not None:
         reducer.append((cs, cs.numel() // N, N, out))
     else:
-        _lib.call("lgnn_reduce_partials", _lib.ptr(cs), cs.numel() // N, N, _lib.ptr(out),
-                  _s(y.device))
+        _lib.call("lgnn_reduce_partials", cs, cs.numel() // N, N, out, _s(y.device))
     return out
 
 
@@ -919,7 +869,7 @@ def bf16_wgrad(dYb: torch.Tensor, X: torch.Tensor, N: int, reducer: list = None)
     if reducer is not None:
         reducer.append((part, S, N * K, dW))
     else:
-        _lib.call("lgnn_reduce_partials", _lib.ptr(part), S, N * K, _lib.ptr(dW), _s(dev))
+        _lib.call("lgnn_reduce_partials", part, S, N * K, dW, _s(dev))
     return dW
 
 
@@ -1274,9 +1224,7 @@ class _GCNStackCE(torch.autograd.Function):
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         pm = torch.empty(B, C, dtype=torch.float32, device=dev)
         wt = torch.empty(B, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_ce_fwd_factors", _lib.ptr(z), _lib.ptr(yy), _lib.ptr(w), B, C,
-                  _lib.ptr(lse), _lib.ptr(out), _lib.ptr(out) + 4, _lib.ptr(bad),
-                  _lib.ptr(pm), _lib.ptr(wt), _s(dev))
+        _lib.call("lgnn_ce_fwd_factors", z, yy, w, B, C, lse, out, out[1:], bad, pm, wt, _s(dev))
         _save(ctx, CeSaved(stack, z, yy, lse, out, w, pm, wt))
         return z, out[0]
 
@@ -1299,8 +1247,7 @@ class _GCNStackCE(torch.autograd.Function):
             return grads(gcn_stack_bwd(sv.stack, None, want_dx, ce=(src, sv.z)))
         B, C = sv.z.shape
         dz = torch.empty_like(sv.z)
-        _lib.call("lgnn_ce_bwd", _lib.ptr(sv.z), _lib.ptr(sv.yy), _lib.ptr(sv.w), B, C,
-                  _lib.ptr(sv.lse), _lib.ptr(sv.out) + 4, _lib.ptr(g), _lib.ptr(dz),
+        _lib.call("lgnn_ce_bwd", sv.z, sv.yy, sv.w, B, C, sv.lse, sv.out[1:], g, dz,
                   _s(sv.z.device))
         if dlogits is not None:
             dz = dz + dlogits
@@ -1334,8 +1281,7 @@ def bn_stats(Z: torch.Tensor) -> torch.Tensor:
     M, N = Z.shape
     sums = torch.empty(2 * N, dtype=torch.float64, device=Z.device)
     ws = _bn_ws(M, N, Z.device)
-    _lib.call("lgnn_bn_stats", _lib.ptr(Z), M, N, _lib.ptr(sums), _lib.ptr(ws), ws.numel(),
-              _s(Z.device))
+    _lib.call("lgnn_bn_stats", Z, M, N, sums, ws, ws.numel(), _s(Z.device))
     return sums
 
 
@@ -1352,26 +1298,21 @@ def bn_finalize(sums, count: float, bn: torch.nn.BatchNorm1d, training: bool, N:
     momentum = bn.momentum if bn.momentum is not None else 0.1
     if nbt is not None and bn.momentum is None:  # cumulative moving average (torch semantics)
         momentum = 1.0 / float(bn.num_batches_tracked.item() + 1)
+    gamma, beta = (bn.weight, bn.bias) if bn.affine else (None, None)
     if part is not None:
-        _lib.call("lgnn_bn_partials_finalize", _lib.ptr(part[0]), part[1], N, _lib.ptr(sums),
-                  float(count), _lib.ptr(bn.weight) if bn.affine else None,
-                  _lib.ptr(bn.bias) if bn.affine else None, float(bn.eps), float(momentum),
-                  _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(nbt), _lib.ptr(mean), _lib.ptr(invstd),
-                  _lib.ptr(scale), _lib.ptr(shift), _s(dev))
+        _lib.call("lgnn_bn_partials_finalize", part[0], part[1], N, sums, float(count), gamma,
+                  beta, float(bn.eps), float(momentum), rm, rv, nbt, mean, invstd, scale, shift,
+                  _s(dev))
         return mean, invstd, scale, shift
-    _lib.call("lgnn_bn_finalize", _lib.ptr(sums), float(count),
-              _lib.ptr(bn.weight) if bn.affine else None, _lib.ptr(bn.bias) if bn.affine else None,
-              float(bn.eps), float(momentum), int(training), N, _lib.ptr(rm), _lib.ptr(rv),
-              _lib.ptr(nbt), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(scale), _lib.ptr(shift),
-              _s(dev))
+    _lib.call("lgnn_bn_finalize", sums, float(count), gamma, beta, float(bn.eps),
+              float(momentum), int(training), N, rm, rv, nbt, mean, invstd, scale, shift, _s(dev))
     return mean, invstd, scale, shift
 
 
 def bn_act(Z, scale, shift, mask=None) -> torch.Tensor:
     M, N = Z.shape
     A = torch.empty_like(Z)
-    _lib.call("lgnn_bn_act", _lib.ptr(Z), M, N, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mask),
-              _lib.ptr(A), _s(Z.device))
+    _lib.call("lgnn_bn_act", Z, M, N, scale, shift, mask, A, _s(Z.device))
     return A
 
 
@@ -1379,9 +1320,8 @@ def bn_bwd_stats(dA, Z, mask, scale, shift, mean, invstd) -> torch.Tensor:
     M, N = Z.shape
     sums = torch.empty(2 * N, dtype=torch.float64, device=Z.device)
     ws = _bn_ws(M, N, Z.device)
-    _lib.call("lgnn_bn_bwd_stats", _lib.ptr(dA), _lib.ptr(Z), _lib.ptr(mask), M, N,
-              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(sums),
-              _lib.ptr(ws), ws.numel(), _s(Z.device))
+    _lib.call("lgnn_bn_bwd_stats", dA, Z, mask, M, N, scale, shift, mean, invstd, sums, ws,
+              ws.numel(), _s(Z.device))
     return sums
 
 
@@ -1390,16 +1330,14 @@ def bn_bwd_apply(dA, Z, mask, scale, shift, mean, invstd, sums, count, training,
     M, N = Z.shape
     dev = Z.device
     dZ = torch.empty_like(Z)
-    _lib.call("lgnn_bn_bwd_apply", _lib.ptr(dA), _lib.ptr(Z), _lib.ptr(mask), M, N,
-              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(sums),
-              float(count), int(training), _lib.ptr(dZ), None, None, _s(dev))
+    _lib.call("lgnn_bn_bwd_apply", dA, Z, mask, M, N, scale, shift, mean, invstd, sums,
+              float(count), int(training), dZ, None, None, _s(dev))
     dg = db = None
     if want_param_grads:
         dg = torch.empty(N, dtype=torch.float32, device=dev)
         db = torch.empty(N, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_bn_bwd_apply", None, None, None, 0, N, _lib.ptr(scale), _lib.ptr(shift),
-                  _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(local_sums), 1.0, 0, None,
-                  _lib.ptr(dg), _lib.ptr(db), _s(dev))
+        _lib.call("lgnn_bn_bwd_apply", None, None, None, 0, N, scale, shift, mean, invstd,
+                  local_sums, 1.0, 0, None, dg, db, _s(dev))
     return dZ, dg, db
 
 
@@ -1466,10 +1404,9 @@ def gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group=N
         Z1 = torch.empty(M, N1, dtype=torch.float32, device=dev)
         S = torch.empty_like(x)
         part = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
-        _lib.call("lgnn_node_linear_fwd_bn", _lib.ptr(x), M, x.size(1), _lib.ptr(csr.rowptr),
-                  _lib.ptr(csr.col), _lib.ptr(csr.w), float(self_scale), W1.data_ptr(),
-                  _lib.ptr(b1), N1, _lib.LGNN_ACT_NONE, _lib.ptr(Z1), _lib.ptr(S),
-                  _lib.ptr(part), None, None, None, None, _s(dev))
+        _lib.call("lgnn_node_linear_fwd_bn", x, M, x.size(1), csr.rowptr, csr.col, csr.w,
+                  float(self_scale), W1, b1, N1, _lib.LGNN_ACT_NONE, Z1, S, part, None, None,
+                  None, None, _s(dev))
         sums = torch.empty(2 * N1, dtype=torch.float64, device=dev)
         count = _global_count(M, group, dev, sync_count)
         if count <= 1:
@@ -1480,8 +1417,7 @@ def gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group=N
         else:
             from .dist import sync_all_reduce
 
-            _lib.call("lgnn_bn_partials_reduce", _lib.ptr(part), P, N1, _lib.ptr(sums), None,
-                      None, _s(dev))
+            _lib.call("lgnn_bn_partials_reduce", part, P, N1, sums, None, None, _s(dev))
             sync_all_reduce(sums, group)
             mean, invstd, scale, shift = bn_finalize(sums, count, bn, training, N1, dev)
     else:
@@ -1503,9 +1439,8 @@ def gin_conv_fwd(x, W1, b1, W2, b2, graph, bn, training, eps, mask, act, group=N
         A1 = torch.empty_like(Z1)
         N2 = W2.size(0)
         H = torch.empty(M, N2, dtype=torch.float32, device=dev)
-        _lib.call("lgnn_node_linear_fwd_bn", _lib.ptr(Z1), M, N1, None, None, None, 0.0,
-                  W2.data_ptr(), _lib.ptr(b2), N2, act, _lib.ptr(H), None, None, _lib.ptr(scale),
-                  _lib.ptr(shift), _lib.ptr(mask), _lib.ptr(A1), _s(dev))
+        _lib.call("lgnn_node_linear_fwd_bn", Z1, M, N1, None, None, None, 0.0, W2, b2, N2, act,
+                  H, None, None, scale, shift, mask, A1, _s(dev))
     else:
         A1 = bn_act(Z1, scale, shift, mask)
         H = linear_fwd(A1, W2, b2, act)
@@ -1552,34 +1487,25 @@ def gin_conv_bwd(sv: GinSaved, dH, want_dx: bool, pool: tuple | None = None,
     P = _lib.load().lgnn_bn_fused_partials(M)
     red: list = []
     fname = "lgnn_node_linear_bwd_bn"
-    w1, w2 = W1.data_ptr(), W2.data_ptr()
     # Lin2 backward; its dX (= dA1) epilogue also sums the BN backward's (g, g xhat)
     dA1 = torch.empty_like(Z1)
     slab2 = torch.empty(P * (N2 * N1 + N2), dtype=torch.float32, device=dev)
     gpart = torch.empty(P * 2 * N1, dtype=torch.float64, device=dev)
+    # from the layer's input A1 to the BN gradient partials: the same in all three entries
+    lin2 = (A1, M, N1, W2, N2, dA1, slab2, slab2[P * N2 * N1:], P, Z1, mask, scale, shift, mean,
+            invstd, gpart)
     if gather is not None:
         dS, tself = gather
-        _lib.call("lgnn_node_linear_bwd_bn_gather", _lib.ptr(dS), _lib.ptr(csr.tptr),
-                  _lib.ptr(csr.tidx), _lib.ptr(csr.tw), float(tself), _lib.ptr(H), sv.act,
-                  _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                  _lib.ptr(gpart), _s(dev))
+        _lib.call("lgnn_node_linear_bwd_bn_gather", dS, csr.tptr, csr.tidx, csr.tw, float(tself),
+                  H, sv.act, *lin2, _s(dev))
     elif pool is not None:
         dlog, W_out, pg, pmean = pool
-        _lib.call("lgnn_node_linear_bwd_bn_pool", _lib.LGNN_BN_GSTATS, None, _lib.ptr(H),
-                  sv.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                  _lib.ptr(gpart), None, 0.0, int(sv.training), _lib.ptr(pg.batch),
-                  _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
+        _lib.call("lgnn_node_linear_bwd_bn_pool", _lib.LGNN_BN_GSTATS, None, H, sv.act, *lin2,
+                  None, 0.0, int(sv.training), pg.batch, pg.gptr, int(pmean), dlog, W_out,
                   W_out.size(0), _s(dev))
     else:
-        _lib.call(fname, _lib.LGNN_BN_GSTATS, _lib.ptr(_f32c(dH)), _lib.ptr(H),
-                  sv.act, _lib.ptr(A1), M, N1, w2, N2, _lib.ptr(dA1), _lib.ptr(slab2),
-                  _lib.ptr(slab2[P * N2 * N1:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd),
-                  _lib.ptr(gpart), None, 0.0, int(sv.training), _s(dev))
+        _lib.call(fname, _lib.LGNN_BN_GSTATS, _f32c(dH), H, sv.act, *lin2, None, 0.0,
+                  int(sv.training), _s(dev))
     dW2 = torch.empty(N2, N1, dtype=torch.float32, device=dev)
     db2 = torch.empty(N2, dtype=torch.float32, device=dev)
     red += [(slab2[:P * N2 * N1], P, N2 * N1, dW2), (slab2[P * N2 * N1:], P, N2, db2)]
@@ -1588,8 +1514,7 @@ def gin_conv_bwd(sv: GinSaved, dH, want_dx: bool, pool: tuple | None = None,
     if sv.affine:  # the affine gradients come out of the same launch (local sums)
         dg = torch.empty(N1, dtype=torch.float32, device=dev)
         dbt = torch.empty(N1, dtype=torch.float32, device=dev)
-    _lib.call("lgnn_bn_partials_reduce", _lib.ptr(gpart), P, N1, _lib.ptr(local),
-              _lib.ptr(dg), _lib.ptr(dbt), _s(dev))
+    _lib.call("lgnn_bn_partials_reduce", gpart, P, N1, local, dg, dbt, _s(dev))
     sums = local
     if sv.training and sv.group is not None:
         from .dist import sync_all_reduce
@@ -1599,11 +1524,9 @@ def gin_conv_bwd(sv: GinSaved, dH, want_dx: bool, pool: tuple | None = None,
     # Lin1 backward with the BN backward applied to dA1 as it is loaded
     dxpre = torch.empty(M, K, dtype=torch.float32, device=dev) if want_dx else None
     slab1 = torch.empty(P * (N1 * K + N1), dtype=torch.float32, device=dev)
-    _lib.call(fname, _lib.LGNN_BN_GIN, _lib.ptr(dA1), None,
-              _lib.LGNN_ACT_NONE, _lib.ptr(S), M, K, w1, N1, _lib.ptr(dxpre),
-              _lib.ptr(slab1), _lib.ptr(slab1[P * N1 * K:]), P, _lib.ptr(Z1), _lib.ptr(mask),
-              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(mean), _lib.ptr(invstd), None,
-              _lib.ptr(sums), float(sv.count), int(sv.training), _s(dev))
+    _lib.call(fname, _lib.LGNN_BN_GIN, dA1, None, _lib.LGNN_ACT_NONE, S, M, K, W1, N1, dxpre,
+              slab1, slab1[P * N1 * K:], P, Z1, mask, scale, shift, mean, invstd, None, sums,
+              float(sv.count), int(sv.training), _s(dev))
     dW1 = torch.empty(N1, K, dtype=torch.float32, device=dev)
     db1 = torch.empty(N1, dtype=torch.float32, device=dev)
     red += [(slab1[:P * N1 * K], P, N1 * K, dW1), (slab1[P * N1 * K:], P, N1, db1)]
@@ -1649,8 +1572,7 @@ def _head_grads(sv, dlogits, jobs: bool):
     dbo = torch.empty(C, dtype=torch.float32, device=dev)
     if jobs:
         return dWo, dbo, [(dlogits, B, C * D, dWo, pooled, D), (dlogits, B, C, dbo)]
-    _lib.call("lgnn_pool_head_bwd", _lib.ptr(dlogits), _lib.ptr(pooled), B, D, _lib.ptr(W_out),
-              C, None, _lib.ptr(dWo), _lib.ptr(dbo), _s(dev))
+    _lib.call("lgnn_pool_head_bwd", dlogits, pooled, B, D, W_out, C, None, dWo, dbo, _s(dev))
     return dWo, dbo, None
 
 
@@ -1868,36 +1790,31 @@ def gat_conv_fwd(x, W, att_src, att_dst, bias, graph, heads, slope, mask, act, b
         # the attention scores come out of the lin GEMM's epilogue (no lgnn_gat_att pass)
         XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
         xg = xg.contiguous()
-        _lib.call("lgnn_bf16_gemm_att", _lib.ptr(xg), int(xg.dtype == torch.float32), M,
-                  xg.size(1),
-                  _lib.ptr(Wb), HC, _lib.ptr(XP), None, _lib.ptr(att_src), _lib.ptr(att_dst),
-                  heads, C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+        _lib.call("lgnn_bf16_gemm_att", xg, int(xg.dtype == torch.float32), M, xg.size(1), Wb, HC,
+                  XP, None, att_src, att_dst, heads, C, a_s, a_d, _s(dev))
     elif plan.mfma:
         XP = bf16_gemm(xg, Wb, None, HC)[0]
     elif plan.scored:
         # split-3 (or one rounded plane) with the attention scores in the GEMM's epilogue
         XP = torch.empty(M, HC, dtype=torch.float32, device=dev)
         xg = xg.contiguous()
-        _lib.call("lgnn_s3_gemm_att", _lib.ptr(xg), M, xg.size(1),
-                  _lib.ptr(wp if wp is not None else dense_planes(Wg, False, False)), HC, 3,
-                  _lib.ptr(XP), _lib.ptr(att_src), _lib.ptr(att_dst), heads,
-                  C, _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+        _lib.call("lgnn_s3_gemm_att", xg, M, xg.size(1),
+                  wp if wp is not None else dense_planes(Wg, False, False), HC, 3, XP, att_src,
+                  att_dst, heads, C, a_s, a_d, _s(dev))
     elif plan.dense:  # split-3 MFMA GEMM (fp32 accuracy), or one rounded plane in bf16 mode
         XP = dense_mm(xg, wp if wp is not None else dense_planes(Wg, False, bf16), HC, None,
                       bf16)
     else:
         XP = linear_fwd(x, W, None, _lib.LGNN_ACT_NONE)
     if not plan.scored:
-        _lib.call("lgnn_gat_att", _lib.ptr(XP), M, heads, C, _lib.ptr(att_src),
-                  _lib.ptr(att_dst), _lib.ptr(a_s), _lib.ptr(a_d), _s(dev))
+        _lib.call("lgnn_gat_att", XP, M, heads, C, att_src, att_dst, a_s, a_d, _s(dev))
     cap = csr.col.numel()
     alpha = torch.empty(cap, heads, dtype=torch.float32, device=dev)
     Y = torch.empty(M, HC, dtype=torch.float32, device=dev)
     # bf16 mode: the kernel also writes Y in bf16 for the next layer's GEMM (no cast pass)
     Yb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) if bf16 and BF16_OUT else None
-    _lib.call("lgnn_gat_fwd", _lib.ptr(csr.rowptr), _lib.ptr(csr.col), _lib.ptr(XP),
-              _lib.ptr(a_s), _lib.ptr(a_d), M, heads, C, float(slope), _lib.ptr(mask),
-              _lib.ptr(bias), act, _lib.ptr(alpha), _lib.ptr(Y), _lib.ptr(Yb), _s(dev))
+    _lib.call("lgnn_gat_fwd", csr.rowptr, csr.col, XP, a_s, a_d, M, heads, C, float(slope), mask,
+              bias, act, alpha, Y, Yb, _s(dev))
     if Yb is not None:
         _remember_bf16(Y, Yb)
     return Y, GatSaved(xg, Wg, att_src, att_dst, XP, a_s, a_d, alpha, Y, mask, wt, wpt, graph,
@@ -1922,27 +1839,20 @@ def gat_conv_bwd(sv: GatSaved, dY, want_dx: bool, pool: tuple | None = None,
     da_d = torch.empty(M, H, dtype=torch.float32, device=dev)
     if pool is not None:
         dlog, W_out, pg, pmean = pool
-        _lib.call("lgnn_gat_bwd_edge_pool", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
-                  _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha), _lib.ptr(mask),
-                  _lib.ptr(Y), sv.act, M, H, C, float(sv.slope), _lib.ptr(pg.batch),
-                  _lib.ptr(pg.gptr), int(pmean), _lib.ptr(dlog), _lib.ptr(W_out),
-                  W_out.size(0), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
+        _lib.call("lgnn_gat_bwd_edge_pool", csr.rowptr, csr.col, XP, a_s, a_d, alpha, mask, Y,
+                  sv.act, M, H, C, float(sv.slope), pg.batch, pg.gptr, int(pmean), dlog, W_out,
+                  W_out.size(0), dZ, da_e, da_d, _s(dev))
     else:
-        _lib.call("lgnn_gat_bwd_edge", _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
-                  _lib.ptr(XP), _lib.ptr(a_s), _lib.ptr(a_d), _lib.ptr(alpha),
-                  _lib.ptr(mask), _lib.ptr(_f32c(dY)), _lib.ptr(Y), sv.act, M, H, C,
-                  float(sv.slope), _lib.ptr(dZ), _lib.ptr(da_e), _lib.ptr(da_d), _s(dev))
+        _lib.call("lgnn_gat_bwd_edge", csr.rowptr, csr.col, XP, a_s, a_d, alpha, mask, _f32c(dY),
+                  Y, sv.act, M, H, C, float(sv.slope), dZ, da_e, da_d, _s(dev))
     P = _lib.load().lgnn_gat_bwd_num_partials(M)
     part = torch.empty(P * 3 * HC, dtype=torch.float32, device=dev)
     dXP = torch.empty_like(XP)
     # bf16 MFMA lin: the kernel also writes dXP in bf16 (the GEMMs' operand, no cast pass)
     dXPb = torch.empty(M, HC, dtype=torch.bfloat16, device=dev) \
         if sv.plan.mfma and BF16_OUT else None
-    _lib.call("lgnn_gat_bwd_node", _lib.ptr(csr.tptr), _lib.ptr(csr.tidx),
-              _lib.ptr(csr.tmap), _lib.ptr(alpha), _lib.ptr(mask), _lib.ptr(da_e),
-              _lib.ptr(da_d), _lib.ptr(dZ), _lib.ptr(XP), _lib.ptr(att_src),
-              _lib.ptr(att_dst), M, H, C, _lib.ptr(dXP), _lib.ptr(part), P, _lib.ptr(dXPb),
-              _s(dev))
+    _lib.call("lgnn_gat_bwd_node", csr.tptr, csr.tidx, csr.tmap, alpha, mask, da_e, da_d, dZ, XP,
+              att_src, att_dst, M, H, C, dXP, part, P, dXPb, _s(dev))
     red = torch.empty(3 * HC, dtype=torch.float32, device=dev)
     if sv.plan.mfma:
         dg = dXPb if dXPb is not None else dXP.to(torch.bfloat16)
@@ -1975,8 +1885,7 @@ def gat_conv_bwd(sv: GatSaved, dY, want_dx: bool, pool: tuple | None = None,
             if extra_red:
                 reduce_multi(jobs, dev)
             else:
-                _lib.call("lgnn_reduce_partials", _lib.ptr(part), P, 3 * HC, _lib.ptr(red),
-                          _s(dev))
+                _lib.call("lgnn_reduce_partials", part, P, 3 * HC, red, _s(dev))
             dx, dW, _ = linear_bwd(_lib.LGNN_GRAD_DIRECT, dXP, H=None,
                                    act=_lib.LGNN_ACT_NONE, X=x, W=W, want_dx=want_dx,
                                    want_db=False)
@@ -2126,8 +2035,8 @@ class _Regression(torch.autograd.Function):
         yc = y.contiguous() if yi64 else y.to(torch.float32).contiguous()
         pred = torch.empty(B, dtype=torch.float32, device=z.device)
         loss = torch.empty((), dtype=torch.float32, device=z.device)
-        _lib.call("lgnn_regression_fwd", _lib.ptr(z), _lib.ptr(yc), int(yi64), B, float(lo),
-                  float(hi), int(smooth), _lib.ptr(pred), _lib.ptr(loss), _s(z.device))
+        _lib.call("lgnn_regression_fwd", z, yc, int(yi64), B, float(lo), float(hi), int(smooth),
+                  pred, loss, _s(z.device))
         ctx.save_for_backward(z, yc)
         ctx.cfg = (int(yi64), B, float(lo), float(hi), int(smooth))
         ctx.set_materialize_grads(False)
@@ -2140,10 +2049,9 @@ class _Regression(torch.autograd.Function):
         dz = torch.empty_like(z)
         if gpred is None and gloss is None:
             return None, None, None, None, None
-        _lib.call("lgnn_regression_bwd", _lib.ptr(z), _lib.ptr(yc), yi64, B, lo, hi, smooth,
-                  _lib.ptr(_f32c(gloss) if gloss is not None else None),
-                  _lib.ptr(_f32c(gpred).reshape(-1) if gpred is not None else None),
-                  _lib.ptr(dz), _s(z.device))
+        _lib.call("lgnn_regression_bwd", z, yc, yi64, B, lo, hi, smooth,
+                  _f32c(gloss) if gloss is not None else None,
+                  _f32c(gpred).reshape(-1) if gpred is not None else None, dz, _s(z.device))
         return dz.view(-1, 1) if ctx.needs_reshape else dz, None, None, None, None
 
 
@@ -2173,8 +2081,7 @@ class _CrossEntropy(torch.autograd.Function):
         out = torch.empty(2, dtype=torch.float32, device=dev)  # loss, sum of weights
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         w = _f32c(weight) if weight is not None else None
-        _lib.call("lgnn_ce_fwd", _lib.ptr(z), _lib.ptr(y), _lib.ptr(w), B, C, _lib.ptr(lse),
-                  _lib.ptr(out), _lib.ptr(out) + 4, _lib.ptr(bad), _s(dev))
+        _lib.call("lgnn_ce_fwd", z, y, w, B, C, lse, out, out[1:], bad, _s(dev))
         if validate and int(bad.item()):
             raise ValueError("cross_entropy: a target is outside [0, num_classes)")
         ctx.save_for_backward(z, y, w, lse, out)
@@ -2186,8 +2093,7 @@ class _CrossEntropy(torch.autograd.Function):
         B, C = z.shape
         dz = torch.empty_like(z)
         g = _f32c(g.reshape(1))
-        _lib.call("lgnn_ce_bwd", _lib.ptr(z), _lib.ptr(y), _lib.ptr(w), B, C, _lib.ptr(lse),
-                  _lib.ptr(out) + 4, _lib.ptr(g), _lib.ptr(dz), _s(z.device))
+        _lib.call("lgnn_ce_bwd", z, y, w, B, C, lse, out[1:], g, dz, _s(z.device))
         return dz, None, None, None
 
 
@@ -2218,17 +2124,16 @@ def sort_pool_fwd(x, graph, k):
     fill = torch.empty(1, dtype=torch.float32, device=dev)
     nws = _lib.load().lgnn_sort_pool_workspace_bytes()
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    _lib.call("lgnn_sort_pool_fwd", _lib.ptr(x), M, D, _lib.ptr(graph.gptr), B, int(k),
-              _lib.ptr(out), _lib.ptr(rank), _lib.ptr(fill), _lib.ptr(ws), nws, _s(dev))
+    _lib.call("lgnn_sort_pool_fwd", x, M, D, graph.gptr, B, int(k), out, rank, fill, ws, nws,
+              _s(dev))
     return out, SortSaved(x, rank, fill, graph, int(k))
 
 
 def sort_pool_bwd(sv: SortSaved, dout):
     M, D = sv.x.shape
     dx = torch.empty_like(sv.x)
-    _lib.call("lgnn_sort_pool_bwd", _lib.ptr(_f32c(dout)), _lib.ptr(sv.x), _lib.ptr(sv.rank),
-              _lib.ptr(sv.graph.batch), _lib.ptr(sv.fill), M, D, sv.k, _lib.ptr(dx),
-              _s(sv.x.device))
+    _lib.call("lgnn_sort_pool_bwd", _f32c(dout), sv.x, sv.rank, sv.graph.batch, sv.fill, M, D,
+              sv.k, dx, _s(sv.x.device))
     return dx
 
 
@@ -2269,8 +2174,8 @@ def cc_pool(features: torch.Tensor, cc: torch.Tensor, num_segments: int, reduce_
     err = torch.empty(1, dtype=torch.int32, device=dev)
     nws = _lib.load().lgnn_cc_pool_workspace_bytes(P, C, num_segments)
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    _lib.call("lgnn_cc_pool", _lib.ptr(f), C, P, _lib.ptr(lab), int(num_segments),
-              int(reduce_max), _lib.ptr(out), None, _lib.ptr(err), _lib.ptr(ws), nws, _s(dev))
+    _lib.call("lgnn_cc_pool", f, C, P, lab, int(num_segments), int(reduce_max), out, None, err,
+              ws, nws, _s(dev))
     if validate and int(err.item()):
         raise IndexError(f"cc_pool: {int(err.item())} labels outside [0, {num_segments})")
     return out

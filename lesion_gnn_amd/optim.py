@@ -9,7 +9,6 @@ No CPU path: parameters and gradients must be contiguous fp32 GPU tensors.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import warnings
 
@@ -68,18 +67,14 @@ class Adam(torch.optim.Optimizer):
 
             for c in range(0, len(ps), MAX_TENSORS):
                 chunk = ps[c:c + MAX_TENSORS]
-                n = len(chunk)
-                arr = ctypes.c_void_p * n
-                args = (n, arr(*[p.data_ptr() for p in chunk]),
-                        arr(*[p.grad.data_ptr() for p in chunk]),
-                        arr(*[self.state[p]["exp_avg"].data_ptr() for p in chunk]),
-                        arr(*[self.state[p]["exp_avg_sq"].data_ptr() for p in chunk]),
-                        (ctypes.c_int64 * n)(*[p.numel() for p in chunk]),
-                        step_t.data_ptr(), ticket.data_ptr(), float(group["lr"]), float(b1),
-                        float(b2), float(group["eps"]), float(group["weight_decay"]),
-                        int(self._decoupled), int(group["maximize"]),
-                        int(c + MAX_TENSORS >= len(ps)))
-                _lib.call("lgnn_adam_step", *args, _lib.stream(dev))
+                _lib.call("lgnn_adam_step", len(chunk), chunk, [p.grad for p in chunk],
+                          [self.state[p]["exp_avg"] for p in chunk],
+                          [self.state[p]["exp_avg_sq"] for p in chunk],
+                          [p.numel() for p in chunk], step_t, ticket, float(group["lr"]),
+                          float(b1), float(b2), float(group["eps"]),
+                          float(group["weight_decay"]), int(self._decoupled),
+                          int(group["maximize"]), int(c + MAX_TENSORS >= len(ps)),
+                          _lib.stream(dev))
         return loss
 
 

@@ -47,9 +47,8 @@ def gaussian_distance(edge_index: torch.Tensor, pos: torch.Tensor, sigma: float,
     E = ei.size(1)
     out = torch.empty(E, dtype=dtype, device=dev)
     err = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.call("lgnn_gaussian_distance", _lib.ptr(pos), int(pos_f64), pos.size(0), pos.size(1),
-              _lib.ptr(ei), E, float(sigma), _lib.ptr(out), int(dtype == torch.float64),
-              _lib.ptr(err), _lib.stream(dev))
+    _lib.call("lgnn_gaussian_distance", pos, int(pos_f64), pos.size(0), pos.size(1), ei, E,
+              float(sigma), out, int(dtype == torch.float64), err, _lib.stream(dev))
     if E and int(err.item()):
         raise IndexError(f"edge_index has {int(err.item())} edges outside [0, {pos.size(0)})")
     return out

@@ -72,10 +72,7 @@ def run():
 
     print(f"{'mask':>5} {'fwd_gather_us':>14} {'fwd_plain_us':>13} {'bwd_transpose_us':>17}")
     for m in MASKS:
-        lib = ctypes.CDLL(os.path.join(OUT, f"liblgnn_{m}.so"))
-        for name, (res, args) in _lib.SIGNATURES.items():
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
+        lib = _lib.bind(ctypes.CDLL(os.path.join(OUT, f"liblgnn_{m}.so")))
 
         def fwd_gather():
             lib.lgnn_node_linear_fwd(b.x.data_ptr(), M, K, csr.rowptr.data_ptr(),

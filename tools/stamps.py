@@ -44,10 +44,7 @@ def run_one(libpath):
     from lesion_gnn_amd import _lib, synth
     from lesion_gnn_amd.graph import Graph
 
-    lib = ctypes.CDLL(libpath)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        f = getattr(lib, name)
-        f.restype, f.argtypes = res, args
+    lib = _lib.bind(ctypes.CDLL(libpath))
     lib.lgnn_debug_stamps.argtypes = [ctypes.c_void_p]
     dev = torch.device("cuda:0")
     b = synth.make_batch(1024, n=64, k=8, d_in=128, seed=0).to(dev)

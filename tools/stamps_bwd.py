@@ -52,10 +52,7 @@ def run():
     s = torch.cuda.current_stream().cuda_stream
     arr = ctypes.c_void_p * (L + 1)
     for v in VARIANTS:
-        lib = ctypes.CDLL(LIB % v)
-        for name, (res, args) in _lib.SIGNATURES.items():
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
+        lib = _lib.bind(ctypes.CDLL(LIB % v))
         P = lib.lgnn_gcn_stack_bwd_partials(M)
         slabs = [torch.empty(P * (D * D + D), device=dev) for _ in range(L + 1)]
         dWp = arr(*[t.data_ptr() for t in slabs])

@@ -69,11 +69,8 @@ def run():
     s = torch.cuda.current_stream().cuda_stream
     arr = ctypes.c_void_p * (L + 1)
     for v in [*VARIANTS, *[p for p in PREBUILT if os.path.exists(LIB % p)]]:
-        lib = ctypes.CDLL(LIB % v)
-        for name, (res, args) in _lib.SIGNATURES.items():
-            f = getattr(lib, name, None)  # a variant built from an older source may lack some
-            if f is not None:
-                f.restype, f.argtypes = res, args
+        # a variant built from an older source may lack some entries
+        lib = _lib.bind(ctypes.CDLL(LIB % v), missing_ok=True)
         P = lib.lgnn_gcn_stack_bwd_partials(M)
         slabs = [torch.empty(P * (D * D + D), device=dev) for _ in range(L + 1)]
         dWp = arr(*[t.data_ptr() for t in slabs])
