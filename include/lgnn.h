@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LGNN_ABI_VERSION 39
+#define LGNN_ABI_VERSION 40
 
 #define LGNN_OK 0
 #define LGNN_EINVAL (-22)
@@ -851,6 +851,99 @@ int lgnn_bf16_gemm_att(const void* A, int a_is_f32, int64_t M, int K, const uint
 int lgnn_bf16_wgrad_partials(int64_t M, int K);
 int lgnn_bf16_wgrad(const uint16_t* dYb, int N, const void* X, int x_is_f32, int64_t M, int K,
                     float* partials, int num_partials, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation: grading metrics accumulated on the device (ABI v40). Replaces: validation_step /
+ * test_step / logits_to_preds of BaseLightningModule (reference models/base.py:190-233), its
+ * torchmetrics collections (:120-145: multiclass Accuracy(micro), CohenKappa(quadratic), macro
+ * F1Score / Precision / Recall) and the referable-DR metrics of metrics.py:7-83 (binary accuracy,
+ * F1, precision, recall, AUROC, average precision of "grade >= 2").
+ *
+ * One evaluator's state is caller-allocated device memory, zero before the first update:
+ *   counts   int64 [C*C + LGNN_EVAL_EXTRA]: the confusion matrix [target][pred], then at
+ *            C*C + LGNN_EVAL_TN / _FP / _FN / _TP the referable counts, at + LGNN_EVAL_NSEEN the
+ *            rows counted and at + LGNN_EVAL_NBAD the rows whose target is outside [0, C);
+ *   loss_acc double [2]: the loss numerator and denominator;
+ *   scores   float [capacity], positive int32 [capacity]: per counted row (in arrival order) the
+ *            referable score and whether its target is referable. Probabilistic mode only.
+ *
+ * lgnn_eval_update: one batch, one launch (one workgroup), graph-capturable. Per row i:
+ *   probabilistic (regression = 0; z [B][C] logits, weight [C] nullable): pred = the lowest index
+ *     among the maxima of z_i (upward scan with a strict >, so a NaN never wins); score =
+ *     sum_{c >= 2} softmax(z_i)[c] (fp32, max subtracted, classes in ascending order); referable
+ *     pred = score > 0.5 (strict: torchmetrics' binary format of probabilities); loss terms
+ *     w[y] (lse - z[y]) and w[y] (lgnn_ce_fwd's, fp32) summed into loss_acc in double;
+ *   regression (regression = 1; z [B]): p = clamp(z_i, 0, C - 1); pred = round(p), half to even
+ *     (torch.round); referable pred = pred >= 2; loss term l(p - y) (smooth_l1 as
+ *     lgnn_regression_fwd) into loss_acc[0], 1 into loss_acc[1]; nothing is stored in scores;
+ *   both: referable target = y >= 2; a target outside [0, C) adds 1 to n_bad and to nothing else.
+ *   The counters are integers (order-independent), the loss sums run in a fixed order, and the
+ *   append offset is read from the device-side n_seen: replays of a captured update append where
+ *   the previous one ended, bit for bit what eager updates give. Rows past `capacity` are counted
+ *   but not stored. 1 <= C <= LGNN_EVAL_MAX_CLASSES, 1 <= B < 2^31.
+ *
+ * lgnn_eval_compute: result [LGNN_EVAL_RESULTS] doubles, once per epoch; a memset and two launches
+ * (probabilistic) or one launch (regression), no host synchronisation. From the counters, in
+ * double: micro accuracy; quadratic kappa 1 - sum w O / sum w E, w = (i - j)^2, E = rows x cols
+ * / n; macro F1 / precision / recall = the mean over the classes with tp + fp + fn > 0
+ * (torchmetrics 1.3.1) of 2tp / (2tp + fp + fn), tp / (tp + fp), tp / (tp + fn); the referable
+ * accuracy, F1, precision, recall; loss = loss_acc[0] / loss_acc[1]. Every zero denominator gives
+ * 0, except kappa's (NaN, as the reference's). From the stored scores, exact AUROC and average
+ * precision by pairwise counting: for each positive i, with gt_i / eq_i = the negatives j with
+ * s_j < s_i / s_j == s_i and tp_i / fp_i = the positives / negatives with s_j >= s_i,
+ *   AUROC = sum_i (gt_i + eq_i / 2) / (n+ n-),   AUPRC = sum_i tp_i / (tp_i + fp_i) / n+
+ * (the tie-aware trapezoid and step integrals of torchmetrics' thresholds=None curves). The pair
+ * counts are integers: each thread owns one sample i, the j side is streamed through LDS in
+ * chunks of LGNN_EVAL_RANK_CHUNK, chunks are dealt over LGNN_EVAL_RANK_SPLIT workgroups per i
+ * block, whose counts meet in per-sample integer atomics; a single workgroup then sums them in a
+ * fixed order. A NaN score compares false with everything, so its sample adds nothing to either
+ * sum. This library's own definition:
+ * AUROC is NaN when n+ == 0 or n- == 0, AUPRC when n+ == 0, and both when the score buffer
+ * overflowed (n_seen > capacity; result[LGNN_EVAL_R_OVERFLOW] = 1) or in regression mode.
+ * workspace: lgnn_eval_workspace_bytes(capacity) bytes, 16-byte aligned (unused in regression
+ * mode).
+ *
+ * lgnn_eval_merge: adds src's counters and loss sums to dst's and appends src's stored scores to
+ * dst's (one launch; both states of the same C and capacity; src unchanged): what one evaluator
+ * fed both streams holds. scores / positive NULL on both sides: a regression state.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_EVAL_MAX_CLASSES 64
+#define LGNN_EVAL_RANK_CHUNK 1024
+#define LGNN_EVAL_RANK_SPLIT 16
+#define LGNN_EVAL_TN 0
+#define LGNN_EVAL_FP 1
+#define LGNN_EVAL_FN 2
+#define LGNN_EVAL_TP 3
+#define LGNN_EVAL_NSEEN 4
+#define LGNN_EVAL_NBAD 5
+#define LGNN_EVAL_EXTRA 6
+#define LGNN_EVAL_R_MICRO_ACC 0
+#define LGNN_EVAL_R_KAPPA 1
+#define LGNN_EVAL_R_MACRO_F1 2
+#define LGNN_EVAL_R_MACRO_PRECISION 3
+#define LGNN_EVAL_R_MACRO_RECALL 4
+#define LGNN_EVAL_R_ACC 5
+#define LGNN_EVAL_R_F1 6
+#define LGNN_EVAL_R_PRECISION 7
+#define LGNN_EVAL_R_RECALL 8
+#define LGNN_EVAL_R_AUROC 9
+#define LGNN_EVAL_R_AUPRC 10
+#define LGNN_EVAL_R_LOSS 11
+#define LGNN_EVAL_R_NSEEN 12
+#define LGNN_EVAL_R_NBAD 13
+#define LGNN_EVAL_R_OVERFLOW 14
+#define LGNN_EVAL_RESULTS 16
+int lgnn_eval_update(const float* z, const int64_t* target, const float* weight, int64_t B, int C,
+                     int regression, int smooth_l1, int64_t* counts, double* loss_acc,
+                     float* scores, int32_t* positive, int64_t capacity, void* stream);
+size_t lgnn_eval_workspace_bytes(int64_t capacity);
+int lgnn_eval_compute(const int64_t* counts, const double* loss_acc, const float* scores,
+                      const int32_t* positive, int64_t capacity, int C, int regression,
+                      double* result, void* workspace, size_t workspace_bytes, void* stream);
+int lgnn_eval_merge(int C, int64_t* counts, double* loss_acc, float* scores, int32_t* positive,
+                    const int64_t* src_counts, const double* src_loss_acc,
+                    const float* src_scores, const int32_t* src_positive, int64_t capacity,
+                    void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,10 @@
 Mirrors the reference's BaseLightningModule contract (src/lesion_gnn/models/base.py:82-233) for
 the parts on the hot path — criterion selection (:88-96), the regression clamp of the
 XLightning.forward methods (gin.py:58-69, gat.py:86-97), training_step (:196-201) and
-configure_optimizers (:162-188) — as a plain nn.Module (Lightning, torchmetrics and W&B are not
-part of this build; metrics/logging are out of scope).
+configure_optimizers (:162-188) — and for evaluation: validation_step / test_step /
+logits_to_preds (:190-233) on the device-side evaluators of lesion_gnn_amd.metrics. A plain
+nn.Module: Lightning, torchmetrics and W&B are not part of this build, so nothing is logged;
+epoch_metrics returns what the reference would log at the end of an epoch.
 """
 from __future__ import annotations
 
@@ -145,6 +147,76 @@ class BaseModule(nn.Module):
         logits = self(batch)
         y = batch.y.float() if self.is_regression else batch.y
         return self.criterion(logits, y)
+
+    # ------------------------------------------------------------------------------------------
+    # evaluation (reference base.py:120-160, :190-233): the metric collections are
+    # lesion_gnn_amd.metrics.GradingMetrics evaluators, one per (stage, dataset), accumulated on
+    # the device and read once per epoch by epoch_metrics
+    # ------------------------------------------------------------------------------------------
+
+    def logits_to_preds(self, logits: torch.Tensor) -> torch.Tensor:
+        """Reference base.py:190-194: logits as they are, or the rounded regression output."""
+        if not self.is_regression:
+            return logits
+        return torch.round(logits).long()
+
+    def evaluator(self, stage: str, dataset_name: str):
+        """The (stage, dataset) evaluator, made on first use (reference base.py:150-160). Kept in
+        a plain dict: neither a buffer nor a submodule, so state_dict(), parameters() and .to()
+        do not see it; its device state is allocated by its first batch."""
+        from ..metrics import GradingMetrics
+
+        evaluators = self.__dict__.setdefault("_evaluators", {})
+        key = (stage, dataset_name)
+        if key not in evaluators:
+            evaluators[key] = GradingMetrics(
+                self.num_classes, self.is_regression, self.loss_type.value,
+                class_weight=getattr(self.criterion, "weight", None))
+        return evaluators[key]
+
+    def _evaluate(self, stage: str, batch, dataloader_idx: int, dataset_name: str | None):
+        with torch.no_grad():  # in whatever train / eval mode the caller set
+            out = self._model_logits(batch)
+        name = str(dataloader_idx) if dataset_name is None else dataset_name
+        # the regression clamp, the rounding / argmax and the criterion's sums run in the update
+        self.evaluator(stage, name).update(out, batch.y)
+        return out
+
+    def validation_step(self, batch, batch_idx: int = 0, dataloader_idx: int = 0,
+                        dataset_name: str | None = None) -> None:
+        """Reference base.py:203-216 (the dataset name is an argument here: there is no trainer
+        to ask; it defaults to str(dataloader_idx)). One model forward and one launch, no host
+        synchronisation; the values are read by epoch_metrics("val")."""
+        self._evaluate("val", batch, dataloader_idx, dataset_name)
+
+    def test_step(self, batch, batch_idx: int = 0, dataloader_idx: int = 0,
+                  dataset_name: str | None = None):
+        """Reference base.py:218-233: (argmax of the logits, or the rounded regression output;
+        batch.y)."""
+        out = self._evaluate("test", batch, dataloader_idx, dataset_name)
+        if not self.is_regression:
+            return torch.argmax(out, dim=1), batch.y
+        out = torch.clamp(out.squeeze(1), min=0, max=self.num_classes - 1)
+        return self.logits_to_preds(out), batch.y
+
+    def epoch_metrics(self, stage: str) -> dict[str, float]:
+        """{f"{stage}_{dataset}_{name}": value} for every dataset evaluated in `stage` since its
+        last reset — the keys the reference logs (e.g. val_DDR_kappa, its monitored metric); the
+        loss only for "val", auroc / auprc only for probabilistic models, as there. The values are
+        those of the epoch's accumulated state (one host read per dataset)."""
+        out = {}
+        for (st, dataset), ev in self.__dict__.get("_evaluators", {}).items():
+            if st != stage or ev.device is None:
+                continue
+            for name, value in ev.compute().items():
+                if name != "loss" or stage == "val":
+                    out[f"{stage}_{dataset}_{name}"] = value
+        return out
+
+    def reset_metrics(self, stage: str) -> None:
+        for (st, _), ev in self.__dict__.get("_evaluators", {}).items():
+            if st == stage:
+                ev.reset()
 
     def configure_optimizers(self):
         """Reference base.py:162-188: the optimizer, plus a torch.optim.lr_scheduler by name or
