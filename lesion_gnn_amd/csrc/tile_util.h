@@ -56,8 +56,8 @@ enum { AGG_GLOBAL = 0,   // index block too large: CSR entries and source rows f
                          // row in the A image, weight bits), rows read from LDS
        AGG_GROWS = 2 };  // sources leave the tile: ow[j] = (global source row, weight bits),
                          // rows gathered from global memory, no index round trip
-// A tile's CSR block in LDS, padded with EB zero-weight entries (source offset / row 0) so a
-// row's batch reads need no bounds logic.
+// A tile's CSR block in LDS, padded with EB zero-weight entries (source offset 0 / the tile's
+// first row) so a row's batch reads need no bounds logic.
 struct TileIdx {
   int rp[TM + 1];
   int2 ow[CAPE_LW + EB];
@@ -200,7 +200,10 @@ __device__ __forceinline__ int idx_store(TileIdx& ti, const IdxRegsT<NTH, CAP>& 
     if (j < R.ne)
       ti.ow[j] = make_int2(any_out ? R.c[u] : (R.c[u] - (int)r0) * LDS, __float_as_int(R.w[u]));
   }
-  if (tid < EB) ti.ow[R.ne + tid] = make_int2(0, 0);
+  // the padding entries (weight 0) name a row the caller has written, the tile's own first:
+  // global row 0 need not be (the open-tile launches' gradient buffers hold the open tiles' rows
+  // only), and 0 x NaN from an unwritten row would poison the row's sum
+  if (tid < EB) ti.ow[R.ne + tid] = make_int2(any_out ? (int)r0 : 0, 0);
   return any_out ? AGG_GROWS : AGG_LOCAL;
 }
 

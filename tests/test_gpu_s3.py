@@ -12,9 +12,9 @@ import numpy as np
 import pytest
 import torch
 
-import oracle.pyg_ref as ref
 from lesion_gnn_amd import _lib, ops, synth
 from lesion_gnn_amd.graph import Graph
+from tests.tile_width_cases import ref_stack64
 
 pytestmark = pytest.mark.gpu
 
@@ -84,19 +84,6 @@ def test_weight_planes_bitexact(cuda, widths):
         got = rec[np.arange(N)[:, None], perm16(np.arange(K))[None, :]]
         # (fp32 subnormals keep fewer bits: absolute floor 2^-133)
         assert np.all(np.abs(got - want) <= 2.0 ** -24 * np.abs(want) + 2.0 ** -133)
-
-
-def ref_stack64(x, edge_index, n, Ws, bs):
-    """float64 restatement of in_proj + L x ELU(GCNConv) (PyG order: lin, propagate, bias)."""
-    ei, w = ref.gcn_norm(edge_index, n)
-    h = x.double() @ Ws[0].double().T + bs[0].double()
-    out = [h]
-    for W, b in zip(Ws[1:], bs[1:]):
-        p = h @ W.double().T
-        agg = torch.zeros_like(p).index_add_(0, ei[1], w.double()[:, None] * p[ei[0]])
-        h = torch.nn.functional.elu(agg + b.double())
-        out.append(h)
-    return out
 
 
 CASES = {
