@@ -945,6 +945,96 @@ int lgnn_eval_merge(int C, int64_t* counts, double* loss_acc, float* scores, int
                     const float* src_scores, const int32_t* src_positive, int64_t capacity,
                     void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Set attention (additive to ABI v40). Replaces: the hot path of PyG 2.5.1
+ * torch_geometric/nn/aggr/utils.py — MultiheadAttentionBlock (torch.nn.MultiheadAttention on
+ * to_dense_batch-padded sets with a key_padding_mask, the residual Linear + ReLU and the two
+ * LayerNorms), SetAttentionBlock, InducedSetAttentionBlock, PoolingByMultiheadAttention — and of
+ * set_transformer.py SetTransformerAggregation, as the reference model composes them
+ * (src/lesion_gnn/models/set_transformer.py:34-66). Sets are ragged: the rows of set g are the
+ * contiguous range a pointer array delimits (Batch.ptr, lgnn_batch_ptr), never padded or masked.
+ *
+ * lgnn_set_attn_fwd: per set g and head h, out = softmax(q_h k_h^T / sqrt(D)) [* mask] v_h.
+ *   q, k, v: fp32 rows with row strides ldq / ldk / ldv (in floats; head h at columns
+ *   [h * D, (h + 1) * D)), so they may be column blocks of one packed projection output.
+ *   Keys / values of set g: rows kptr[g] .. kptr[g + 1], or (kptr NULL) k_rows rows per set at
+ *   row g * k_rows. Queries: rows qptr[g] .. qptr[g + 1]; or (qptr NULL) q_rows rows per set at
+ *   row g * q_rows; or (qptr NULL, q_shared = 1) the SAME q_rows rows [0, q_rows) of q for every
+ *   set (PMA's seed points, ISAB's inducing points: no per-set copy of q). out [rows][H * D]
+ *   contiguous, rows as the queries' (shared: num_sets * q_rows, set g at row g * q_rows);
+ *   lse [rows][H]: the log-sum-exp of each (query row, head)'s scaled scores. No score or
+ *   probability matrix is written. A set without keys gives zero output rows (lse 0).
+ *   mask (nullable, with mask_off): attention-probability dropout keep-mask already scaled by
+ *   1 / (1 - p) (torch.nn.MultiheadAttention(dropout = p) in training: the probabilities are
+ *   dropped after the softmax), laid out [set][head][query][key]: element
+ *   mask[mask_off[g] + (h * nq_g + i) * nk_g + j]; mask_off int64 [num_sets + 1] from
+ *   lgnn_set_attn_mask_offsets (mask_off[num_sets] = the mask's size). The mask is a span of one
+ *   lgnn_dropout_masks launch.
+ *   1 <= D <= LGNN_SET_ATTN_MAX_D, H * D <= LGNN_SET_ATTN_MAX_HD, else LGNN_EINVAL. Query rows
+ *   are processed in blocks of LGNN_SET_ATTN_QROWS and key rows in blocks of
+ *   LGNN_SET_ATTN_KROWS, in a fixed order with a running maximum and sum: any set size.
+ * lgnn_set_attn_bwd: dq, dk, dv (row strides lddq / lddk / lddv, the layouts of q, k, v) from
+ *   dout, with the probabilities recomputed from q, k and lse; out is the forward's output. For
+ *   shared queries dq is PER SET, [num_sets * q_rows] rows (set g at row g * q_rows): the caller
+ *   sums the sets in fixed order (lgnn_reduce_partials with num_partials = num_sets,
+ *   len = q_rows * lddq). Every row of dq, dk, dv is written (zeros for a set without keys or
+ *   without queries). No atomics: two runs agree bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_SET_ATTN_QROWS 16
+#define LGNN_SET_ATTN_KROWS 32
+#define LGNN_SET_ATTN_MAX_D 128
+#define LGNN_SET_ATTN_MAX_HD 512
+int lgnn_set_attn_mask_offsets(const int32_t* qptr, int q_rows, const int32_t* kptr, int k_rows,
+                               int64_t num_sets, int heads, int64_t* mask_off, void* stream);
+int lgnn_set_attn_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                      int64_t ldv, const int32_t* qptr, int q_rows, int q_shared,
+                      const int32_t* kptr, int k_rows, int64_t num_sets, int heads, int head_dim,
+                      const float* mask, const int64_t* mask_off, float* out, float* lse,
+                      void* stream);
+int lgnn_set_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                      int64_t ldv, const int32_t* qptr, int q_rows, int q_shared,
+                      const int32_t* kptr, int k_rows, int64_t num_sets, int heads, int head_dim,
+                      const float* mask, const int64_t* mask_off, const float* out,
+                      const float* dout, const float* lse, float* dq, int64_t lddq, float* dk,
+                      int64_t lddk, float* dv, int64_t lddv, void* stream);
+
+/* Residual + activation + LayerNorm: y = LN(a + act(b)) over rows of C <= 512 channels.
+ * Replaces: MultiheadAttentionBlock's `out = out + x; out = layer_norm1(out)` and
+ * `out = out + lin(out).relu(); out = layer_norm2(out)` (PyG aggr/utils.py) and PMA's
+ * `lin(x).relu()` — torch.nn.LayerNorm(C) (biased variance, eps), F.relu, the adds and their
+ * autograd. act: LGNN_ACT_NONE or LGNN_ACT_RELU. a: [M][C]; or (a_rows > 0) [a_rows][C] broadcast,
+ * row r reading a[r % a_rows] (the shared seed / inducing rows); or NULL (y = LN(act(b))).
+ * gamma / beta NULL: no LayerNorm (y = a + act(b)); else mean / rstd [M] are written for the
+ * backward. 0 <= M < 2^31.
+ * lgnn_res_norm_bwd: da, db (each nullable) [M][C] — db through the activation, da PER ROW also
+ *   for a broadcast a (the caller sums the sets in fixed order: lgnn_reduce_partials with
+ *   num_partials = M / a_rows, len = a_rows * C) — and, with gamma, the column sums
+ *   part [2][num_partials][C] = (dgamma, dbeta) per workgroup in fixed order, each summed by
+ *   lgnn_reduce_partials(.., num_partials, C); num_partials = lgnn_res_norm_bwd_partials(M).
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_ACT_RELU 2
+int lgnn_res_norm_fwd(const float* a, int a_rows, const float* b, int act, const float* gamma,
+                      const float* beta, float eps, int64_t M, int C, float* y, float* mean,
+                      float* rstd, void* stream);
+int lgnn_res_norm_bwd_partials(int64_t M);
+int lgnn_res_norm_bwd(const float* a, int a_rows, const float* b, int act, const float* gamma,
+                      int64_t M, int C, const float* mean, const float* rstd, const float* dy,
+                      float* da, float* db, float* part, int num_partials, void* stream);
+
+/* Set readout over x [num_sets * rows][C]. Replaces SetTransformerAggregation's
+ * `x.nan_to_num()` + `x.flatten(1, 2) if concat else x.mean(dim=1)` (PyG set_transformer.py) and
+ * the reference model's mean (set_transformer.py:64). mean = 1: out [num_sets][C] = the mean of a
+ * set's rows; 0: out = x. gptr (nullable, int32 [num_sets + 1], the INPUT sets' offsets): a set
+ * with no input row gives zeros (what nan_to_num leaves of PyG's fully masked softmax) and gets
+ * zero gradient. lgnn_set_readout_bwd: dx [num_sets * rows][C]. */
+int lgnn_set_readout_fwd(const float* x, const int32_t* gptr, int64_t num_sets, int rows, int C,
+                         int mean, float* out, void* stream);
+int lgnn_set_readout_bwd(const float* dout, const int32_t* gptr, int64_t num_sets, int rows,
+                         int C, int mean, float* dx, void* stream);
+/* y = a + b over n floats (y may alias a or b): where two gradient paths meet at a block's input
+ * (the residual's and the projection's: autograd's AccumulateGrad add). */
+int lgnn_add(const float* a, const float* b, float* y, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,15 +7,18 @@ include/lgnn.h). GPU only — there is no CPU fallback.
 """
 from . import _lib
 from . import library  # noqa: F401  (registers the lgnn:: custom ops for torch.compile)
-from .conv import GCNConv, GraphConv, global_add_pool, global_mean_pool
+from .conv import (GCNConv, GraphConv, SetTransformerAggregation, global_add_pool,
+                   global_mean_pool)
 from .graph import Graph
 from .knn import KNNGraph, knn_graph
 from .metrics import GradingMetrics
 from .transforms import GaussianDistance, SaveAs, gaussian_distance
-from .models import GCN, GCNConfig, get_model
+from .models import (GCN, GCNConfig, SetTransformer, SetTransformerModelConfig,
+                     get_model)
 
 __all__ = ["GCN", "GCNConfig", "GCNConv", "GaussianDistance", "GradingMetrics", "Graph",
-           "GraphConv", "KNNGraph", "SaveAs", "gaussian_distance", "get_model", "global_mean_pool",
+           "GraphConv", "KNNGraph", "SaveAs", "SetTransformer", "SetTransformerAggregation",
+           "SetTransformerModelConfig", "gaussian_distance", "get_model", "global_mean_pool",
            "global_add_pool", "knn_graph", "load_library"]
 
 

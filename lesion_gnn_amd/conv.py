@@ -250,3 +250,264 @@ class SortAggregation(nn.Module):
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}(k={self.k})"
+
+
+# ----------------------------------------------------------------------------------------------
+# Set attention: PyG 2.5.1 torch_geometric/nn/aggr/utils.py + set_transformer.py on ragged sets
+# (the rows of a set are contiguous, delimited by Batch.ptr; nothing is padded or masked).
+# The nn.MultiheadAttention / nn.Linear / nn.LayerNorm members are parameter containers with
+# PyG's state_dict keys; their forward is never called (ops.mab runs the HIP kernels).
+# ----------------------------------------------------------------------------------------------
+
+
+def _ragged_self_mask_numel(ptr: torch.Tensor, heads: int) -> int:
+    """heads * sum_g n_g^2: the attention-dropout mask of a SetAttentionBlock over ragged sets.
+    The size depends on the set sizes, so it is read from the device (one synchronisation):
+    eager mode only."""
+    if torch.compiler.is_compiling() or torch.cuda.is_current_stream_capturing():
+        raise NotImplementedError(
+            "attention dropout of a SetAttentionBlock over ragged sets sizes its mask from the "
+            "set sizes (a host read): not available under torch.compile or graph capture")
+    n = (ptr[1:] - ptr[:-1]).to(torch.int64)
+    return int((n * n).sum().item()) * heads
+
+
+def draw_attention_masks(state: torch.Tensor, numels: list, key: str) -> list:
+    """One flat dropout mask per attention site (site j from stream j of its launch, the sites in
+    execution order), lgnn.h's LGNN_MAX_MASKS per launch."""
+    out = []
+    for i in range(0, len(numels), dropout.MAX_MASKS):
+        out += dropout.masks(state, [(n,) for n in numels[i:i + dropout.MAX_MASKS]], key)
+    return out
+
+
+class MultiheadAttentionBlock(nn.Module):
+    """PyG MultiheadAttentionBlock(channels, heads, layer_norm, dropout): keys `attn.*`, `lin.*`,
+    `layer_norm1.*`, `layer_norm2.*`. forward(x, y, form): x the query rows, y the key rows (None:
+    y is x), form the ops.AttnForm saying which rows belong to which set."""
+
+    sites = 1  # attention-dropout sites of one forward
+
+    def __init__(self, channels: int, heads: int = 1, layer_norm: bool = True,
+                 dropout: float = 0.0):
+        super().__init__()
+        self.channels, self.heads, self.dropout = channels, heads, float(dropout)
+        self.attn = nn.MultiheadAttention(channels, heads, batch_first=True, dropout=dropout)
+        self.lin = nn.Linear(channels, channels)
+        self.layer_norm1 = nn.LayerNorm(channels) if layer_norm else None
+        self.layer_norm2 = nn.LayerNorm(channels) if layer_norm else None
+        self._dropout_key = repr(self.dropout)
+
+    def reset_parameters(self):
+        self.attn._reset_parameters()
+        self.lin.reset_parameters()
+        if self.layer_norm1 is not None:
+            self.layer_norm1.reset_parameters()
+            self.layer_norm2.reset_parameters()
+
+    def params(self) -> list:
+        ln = [None] * 4 if self.layer_norm1 is None else [
+            self.layer_norm1.weight, self.layer_norm1.bias, self.layer_norm2.weight,
+            self.layer_norm2.bias]
+        return [self.attn.in_proj_weight, self.attn.in_proj_bias, self.attn.out_proj.weight,
+                self.attn.out_proj.bias, self.lin.weight, self.lin.bias] + ln
+
+    def mask_numel(self, form: ops.AttnForm, Mq: int, Mk: int):
+        n = ops.set_attn_mask_numel(form, self.heads, Mq, Mk)
+        return n if n is not None else _ragged_self_mask_numel(form.qptr, self.heads)
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor | None, form: ops.AttnForm,
+                mask: torch.Tensor | None = None) -> torch.Tensor:
+        if mask is None and self.training and self.dropout > 0.0:
+            # a lone block: its mask from the per-device generator (a model draws all of its
+            # forward's masks in one launch and passes them in)
+            k = x if y is None else y
+            mask = draw_attention_masks(dropout.global_state(x.device),
+                                        [self.mask_numel(form, x.size(0), k.size(0))],
+                                        dropout.key(self, self.dropout))[0]
+        return ops.mab(x, y, self.params(), form, self.heads, mask)
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__}({self.channels}, heads={self.heads}, "
+                f"layer_norm={self.layer_norm1 is not None}, dropout={self.dropout})")
+
+
+def _set_form(ptr, num_sets: int, rows: int) -> tuple:
+    """(ptr, rows per set) of a row layout: ragged by ptr, or `rows` rows per set."""
+    return (ptr, 0) if ptr is not None else (None, int(rows))
+
+
+class SetAttentionBlock(nn.Module):
+    """PyG SetAttentionBlock: mab(x, x) per set. Key prefix `mab.`. The sets are ragged (ptr,
+    Batch.ptr as int32) or hold `rows` rows each (ptr None)."""
+
+    sites = 1
+
+    def __init__(self, channels: int, heads: int = 1, layer_norm: bool = True,
+                 dropout: float = 0.0):
+        super().__init__()
+        self.mab = MultiheadAttentionBlock(channels, heads, layer_norm, dropout)
+
+    def reset_parameters(self):
+        self.mab.reset_parameters()
+
+    def form(self, ptr, num_sets: int, rows: int = 0) -> ops.AttnForm:
+        p, r = _set_form(ptr, num_sets, rows)
+        return ops.AttnForm(p, r, False, p, r, num_sets)
+
+    def mask_numels(self, M: int, ptr, num_sets: int, rows: int = 0) -> list:
+        return [self.mab.mask_numel(self.form(ptr, num_sets, rows), M, M)]
+
+    def forward(self, x, ptr=None, num_sets: int | None = None, rows: int = 0, masks=None):
+        return self.mab(x, None, self.form(ptr, num_sets, rows),
+                        masks[0] if masks is not None else None)
+
+
+class InducedSetAttentionBlock(nn.Module):
+    """PyG InducedSetAttentionBlock: h = mab1(ind, x) (the same m inducing rows query every set),
+    out = mab2(x, h). Keys `ind`, `mab1.*`, `mab2.*`."""
+
+    sites = 2
+
+    def __init__(self, channels: int, num_induced_points: int, heads: int = 1,
+                 layer_norm: bool = True, dropout: float = 0.0):
+        super().__init__()
+        self.ind = nn.Parameter(torch.empty(1, num_induced_points, channels))
+        self.mab1 = MultiheadAttentionBlock(channels, heads, layer_norm, dropout)
+        self.mab2 = MultiheadAttentionBlock(channels, heads, layer_norm, dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot_(self.ind)
+        self.mab1.reset_parameters()
+        self.mab2.reset_parameters()
+
+    def forms(self, ptr, num_sets: int, rows: int = 0):
+        p, r = _set_form(ptr, num_sets, rows)
+        m = self.ind.size(1)
+        return (ops.AttnForm(None, m, True, p, r, num_sets),
+                ops.AttnForm(p, r, False, None, m, num_sets))
+
+    def mask_numels(self, M: int, ptr, num_sets: int, rows: int = 0) -> list:
+        f1, f2 = self.forms(ptr, num_sets, rows)
+        m = self.ind.size(1)
+        return [self.mab1.mask_numel(f1, m, M), self.mab2.mask_numel(f2, M, num_sets * m)]
+
+    def forward(self, x, ptr=None, num_sets: int | None = None, rows: int = 0, masks=None):
+        m1, m2 = masks if masks is not None else (None, None)
+        if masks is None and self.training and self.mab1.dropout > 0.0:
+            # a lone block: its masks from the per-device generator
+            m1, m2 = draw_attention_masks(dropout.global_state(x.device),
+                                          self.mask_numels(x.size(0), ptr, num_sets, rows),
+                                          dropout.key(self.mab1, self.mab1.dropout))
+        p, r = _set_form(ptr, num_sets, rows)
+        return ops.isab(x, self.ind.view(self.ind.size(1), -1), self.mab1.params(),
+                        self.mab2.params(), p, r, num_sets, self.mab1.heads, m1, m2)
+
+
+class PoolingByMultiheadAttention(nn.Module):
+    """PyG PoolingByMultiheadAttention: mab(seed, relu(lin(x))), S rows per set. Keys `lin.*`,
+    `seed`, `mab.*`. Output [num_sets * S, channels], set g at rows [g * S, (g + 1) * S)."""
+
+    sites = 1
+
+    def __init__(self, channels: int, num_seed_points: int = 1, heads: int = 1,
+                 layer_norm: bool = True, dropout: float = 0.0):
+        super().__init__()
+        self.lin = nn.Linear(channels, channels)
+        self.seed = nn.Parameter(torch.empty(1, num_seed_points, channels))
+        self.mab = MultiheadAttentionBlock(channels, heads, layer_norm, dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.lin.reset_parameters()
+        glorot_(self.seed)
+        self.mab.reset_parameters()
+
+    def form(self, ptr, num_sets: int, rows: int = 0) -> ops.AttnForm:
+        p, r = _set_form(ptr, num_sets, rows)
+        return ops.AttnForm(None, self.seed.size(1), True, p, r, num_sets)
+
+    def mask_numels(self, M: int, ptr, num_sets: int, rows: int = 0) -> list:
+        return [self.mab.mask_numel(self.form(ptr, num_sets, rows), self.seed.size(1), M)]
+
+    def forward(self, x, ptr=None, num_sets: int | None = None, rows: int = 0, masks=None):
+        x = ops.res_norm(None, ops.linear_auto(x, self.lin.weight, self.lin.bias),
+                         _lib.LGNN_ACT_RELU)
+        return self.mab(self.seed.view(self.seed.size(1), -1), x, self.form(ptr, num_sets, rows),
+                        masks[0] if masks is not None else None)
+
+
+class SetTransformerAggregation(nn.Module):
+    """PyG 2.5.1 SetTransformerAggregation (the readout of the reference's
+    GAT(num_st_seed_points=...), gat.py:33-43): SAB x E over each set -> PMA (S seed rows per set)
+    -> SAB x D over those rows -> [B, S * channels] (concat) or the mean over the S rows. A set
+    with no rows gives a zero output row (what PyG's nan_to_num leaves). Keys `encoders.i.mab.*`,
+    `pma.*`, `decoders.i.mab.*`. `index` must be sorted (PyG Batch order)."""
+
+    def __init__(self, channels: int, num_seed_points: int = 1, num_encoder_blocks: int = 1,
+                 num_decoder_blocks: int = 1, heads: int = 1, concat: bool = True,
+                 layer_norm: bool = False, dropout: float = 0.0):
+        super().__init__()
+        self.channels, self.num_seed_points, self.heads = channels, num_seed_points, heads
+        self.concat, self.layer_norm, self.dropout = concat, layer_norm, float(dropout)
+        self.encoders = nn.ModuleList([SetAttentionBlock(channels, heads, layer_norm, dropout)
+                                       for _ in range(num_encoder_blocks)])
+        self.pma = PoolingByMultiheadAttention(channels, num_seed_points, heads, layer_norm,
+                                               dropout)
+        self.decoders = nn.ModuleList([SetAttentionBlock(channels, heads, layer_norm, dropout)
+                                       for _ in range(num_decoder_blocks)])
+        self._dropout_key = repr(self.dropout)
+        self.register_buffer("_dropout_rng", dropout_state(self), persistent=False)
+
+    def reset_parameters(self):
+        for m in (*self.encoders, self.pma, *self.decoders):
+            m.reset_parameters()
+
+    def forward(self, x: torch.Tensor, index: torch.Tensor | None = None,
+                ptr: torch.Tensor | None = None, dim_size: int | None = None, dim: int = -2, *,
+                graph: Graph | None = None) -> torch.Tensor:
+        if dim not in (-2, 0) or x.dim() != 2:
+            raise ValueError("SetTransformerAggregation: x must be [num_nodes, channels], dim=-2")
+        if graph is None:
+            if index is None:
+                raise ValueError("SetTransformerAggregation needs the batch index (or a Graph)")
+            graph = _pool_graph(x, index, dim_size)
+        gptr, B, S, M = graph.gptr, graph.num_graphs, self.num_seed_points, x.size(0)
+        masks = _set_masks(self, [(b, (M, gptr, B)) for b in self.encoders]
+                           + [(self.pma, (M, gptr, B))]
+                           + [(b, (B * S, None, B, S)) for b in self.decoders])
+        for blk in self.encoders:
+            x = blk(x, gptr, B, masks=masks.pop(0))
+        x = self.pma(x, gptr, B, masks=masks.pop(0))
+        for blk in self.decoders:
+            x = blk(x, None, B, S, masks=masks.pop(0))
+        return ops.set_readout(x, gptr, B, S, not self.concat)
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__}({self.channels}, num_seed_points="
+                f"{self.num_seed_points}, heads={self.heads}, layer_norm={self.layer_norm}, "
+                f"dropout={self.dropout})")
+
+
+def dropout_state(module: nn.Module) -> torch.Tensor:
+    """A module's attention-dropout generator state, seeded as the models' (from the default
+    generator's state and the module's initial parameters, without drawing)."""
+    return dropout.new_state(salt=dropout.param_salt(module))
+
+
+def _set_masks(owner: nn.Module, blocks: list) -> list:
+    """Per block of `blocks` [(block, mask_numels arguments)] the list of its attention-dropout
+    masks (None when dropout is inactive), all drawn from owner._dropout_rng with one launch per
+    LGNN_MAX_MASKS sites, site j of a launch from stream j, the sites in execution order."""
+    if owner.dropout == 0.0 or not owner.training:
+        return [None] * len(blocks)
+    numels = []
+    for blk, args in blocks:
+        numels += blk.mask_numels(*args)
+    flat = draw_attention_masks(owner._dropout_rng, numels, dropout.key(owner, owner.dropout))
+    out = []
+    for blk, _ in blocks:
+        out.append(flat[:blk.sites])
+        flat = flat[blk.sites:]
+    return out

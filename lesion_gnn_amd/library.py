@@ -839,3 +839,320 @@ sort_pool.register_autograd(_sort_backward, setup_context=_sort_setup)
 
 def gparts_empty(dev) -> list[Tensor]:
     return [_none(dev) for _ in GPARTS]
+
+
+# ----------------------------------------------------------------------------------------------
+# Set attention: MultiheadAttentionBlock as one op, the residual / activation / LayerNorm kernel,
+# the set readout
+# ----------------------------------------------------------------------------------------------
+
+
+def _mab_params(wb: list[Tensor], ln: list[Tensor]) -> list:
+    return list(wb) + (list(ln) if len(ln) else [None] * 4)
+
+
+def _mab_rows(x, qptr, q_rows, num_sets):
+    return x.shape[0] if qptr is not None else num_sets * q_rows
+
+
+@custom_op("lgnn::mab", mutates_args=(), device_types="cuda")
+def mab(x: Tensor, y: Optional[Tensor], wb: list[Tensor], ln: list[Tensor],
+        qptr: Optional[Tensor], kptr: Optional[Tensor], q_rows: int, q_shared: bool, k_rows: int,
+        num_sets: int, heads: int, mask: Optional[Tensor]) -> list[Tensor]:
+    """[out, *ops.MAB_SAVED] (absent members as 0-element uint8 tensors)."""
+    form = ops.AttnForm(qptr, q_rows, q_shared, kptr, k_rows, num_sets)
+    out, sv = ops.mab_fwd(x, y, _mab_params(wb, ln), form, heads, mask)
+    return [out] + [_enc(getattr(sv, n), x.device) for n in ops.MAB_SAVED]
+
+
+@mab.register_fake
+def _(x, y, wb, ln, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask):
+    C = wb[0].shape[1]
+    R = _mab_rows(x, qptr, q_rows, num_sets)
+    return [x.new_empty(R, C)] + _mab_saved_fake(x, y, C, R, heads, len(ln) > 0, mask, num_sets)
+
+
+@custom_op("lgnn::mab_bwd", mutates_args=(), device_types="cuda")
+def mab_bwd(dout: Tensor, x: Tensor, y: Optional[Tensor], wb: list[Tensor], ln: list[Tensor],
+            saved: list[Tensor], qptr: Optional[Tensor], kptr: Optional[Tensor], q_rows: int,
+            q_shared: bool, k_rows: int, num_sets: int, heads: int, mask: Optional[Tensor],
+            want_dx: bool, want_dy: bool) -> list[Tensor]:
+    """[dx, dy, the six weight / bias gradients, the four LayerNorm gradients] (absent: empty)."""
+    form = ops.AttnForm(qptr, q_rows, q_shared, kptr, k_rows, num_sets)
+    sv = ops.MabSaved(x.contiguous(), y.contiguous() if y is not None else None,
+                      [p.contiguous() if p is not None else None for p in _mab_params(wb, ln)],
+                      form, heads, mask, *[_opt(t) for t in saved])
+    dx, dy, dps = ops.mab_bwd(sv, dout, want_dx, want_dy)
+    return _grad_list([dx, dy] + dps, x.device)
+
+
+@mab_bwd.register_fake
+def _(dout, x, y, wb, ln, saved, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask,
+      want_dx, want_dy):
+    none = lambda: x.new_empty(0, dtype=torch.uint8)  # noqa: E731
+    return [torch.empty_like(x) if want_dx else none(),
+            torch.empty_like(y) if (y is not None and want_dy) else none()] + \
+        [torch.empty_like(p) for p in wb] + \
+        ([torch.empty_like(p) for p in ln] if len(ln) else [none() for _ in range(4)])
+
+
+def _mab_setup(ctx, inputs, output):
+    x, y, wb, ln, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask = inputs
+    ts = [x, y, qptr, kptr, mask]
+    ctx.present = [t is not None for t in ts]
+    ctx.counts = (len(wb), len(ln))
+    ctx.save_for_backward(*[t for t in ts if t is not None], *wb, *ln, *output[1:])
+    ctx.meta = (q_rows, q_shared, k_rows, num_sets, heads)
+
+
+def _mab_backward(ctx, grads):
+    st = list(ctx.saved_tensors)
+    x, y, qptr, kptr, mask = [st.pop(0) if p else None for p in ctx.present]
+    nwb, nln = ctx.counts
+    wb, ln, saved = st[:nwb], st[nwb:nwb + nln], st[nwb + nln:]
+    q_rows, q_shared, k_rows, num_sets, heads = ctx.meta
+    need = ctx.needs_input_grad
+    g = torch.ops.lgnn.mab_bwd(grads[0], x, y, wb, ln, saved, qptr, kptr, q_rows, q_shared,
+                               k_rows, num_sets, heads, mask, need[0], need[1] and y is not None)
+    return (_opt(g[0]), _opt(g[1]), list(g[2:2 + nwb]), list(g[8:8 + nln]) if nln else [],
+            None, None, None, None, None, None, None, None)
+
+
+mab.register_autograd(_mab_backward, setup_context=_mab_setup)
+
+
+@custom_op("lgnn::res_norm", mutates_args=(), device_types="cuda")
+def res_norm(a: Optional[Tensor], b: Tensor, act: int, gamma: Optional[Tensor],
+             beta: Optional[Tensor], a_rows: int, eps: float) -> list[Tensor]:
+    """[y, mean, rstd]"""
+    y, sv = ops.res_norm_fwd(a, a_rows, b, act, gamma, beta, eps)
+    return [y, _enc(sv.mean, b.device), _enc(sv.rstd, b.device)]
+
+
+@res_norm.register_fake
+def _(a, b, act, gamma, beta, a_rows, eps):
+    stat = (lambda: b.new_empty(b.shape[0])) if gamma is not None else \
+        (lambda: b.new_empty(0, dtype=torch.uint8))
+    return [torch.empty_like(b), stat(), stat()]
+
+
+@custom_op("lgnn::res_norm_bwd", mutates_args=(), device_types="cuda")
+def res_norm_bwd(dy: Tensor, a: Optional[Tensor], b: Tensor, act: int, gamma: Optional[Tensor],
+                 mean: Tensor, rstd: Tensor, a_rows: int, want_da: bool,
+                 want_db: bool) -> list[Tensor]:
+    sv = ops.NormSaved(a.contiguous() if a is not None else None, a_rows, b.contiguous(), act,
+                       gamma.contiguous() if gamma is not None else None, _opt(mean), _opt(rstd))
+    return _grad_list(ops.res_norm_bwd(sv, dy, want_da, want_db), b.device)
+
+
+@res_norm_bwd.register_fake
+def _(dy, a, b, act, gamma, mean, rstd, a_rows, want_da, want_db):
+    none = lambda: b.new_empty(0, dtype=torch.uint8)  # noqa: E731
+    return [torch.empty_like(a) if (a is not None and want_da) else none(),
+            torch.empty_like(b) if want_db else none(),
+            torch.empty_like(gamma) if gamma is not None else none(),
+            torch.empty_like(gamma) if gamma is not None else none()]
+
+
+def _res_norm_setup(ctx, inputs, output):
+    a, b, act, gamma, beta, a_rows, eps = inputs
+    ts = [a, gamma]
+    ctx.present = [t is not None for t in ts]
+    ctx.save_for_backward(*[t for t in ts if t is not None], b, output[1], output[2])
+    ctx.meta = (act, a_rows)
+
+
+def _res_norm_backward(ctx, grads):
+    st = list(ctx.saved_tensors)
+    a, gamma = [st.pop(0) if p else None for p in ctx.present]
+    b, mean, rstd = st
+    act, a_rows = ctx.meta
+    need = ctx.needs_input_grad
+    da, db, dg, dbt = torch.ops.lgnn.res_norm_bwd(grads[0], a, b, act, gamma, mean, rstd, a_rows,
+                                                  need[0] and a is not None, need[1])
+    return _opt(da), _opt(db), None, _opt(dg), _opt(dbt), None, None
+
+
+res_norm.register_autograd(_res_norm_backward, setup_context=_res_norm_setup)
+
+
+@custom_op("lgnn::set_readout", mutates_args=(), device_types="cuda")
+def set_readout(x: Tensor, gptr: Optional[Tensor], num_sets: int, rows: int,
+                mean: bool) -> Tensor:
+    return ops.set_readout_fwd(x, gptr, num_sets, rows, mean)
+
+
+@set_readout.register_fake
+def _(x, gptr, num_sets, rows, mean):
+    return x.new_empty(num_sets, x.shape[1] if mean else rows * x.shape[1])
+
+
+@custom_op("lgnn::set_readout_bwd", mutates_args=(), device_types="cuda")
+def set_readout_bwd(dout: Tensor, gptr: Optional[Tensor], num_sets: int, rows: int, C: int,
+                    mean: bool) -> Tensor:
+    return ops.set_readout_bwd(dout, gptr, num_sets, rows, C, mean)
+
+
+@set_readout_bwd.register_fake
+def _(dout, gptr, num_sets, rows, C, mean):
+    return dout.new_empty(num_sets * rows, C)
+
+
+def _readout_setup(ctx, inputs, output):
+    x, gptr, num_sets, rows, mean = inputs
+    ctx.has_gptr = gptr is not None
+    if ctx.has_gptr:
+        ctx.save_for_backward(gptr)
+    ctx.meta = (num_sets, rows, x.shape[1], mean)
+
+
+def _readout_backward(ctx, dout):
+    gptr = ctx.saved_tensors[0] if ctx.has_gptr else None
+    return torch.ops.lgnn.set_readout_bwd(dout, gptr, *ctx.meta), None, None, None, None
+
+
+set_readout.register_autograd(_readout_backward, setup_context=_readout_setup)
+
+
+
+def _isab_params(wb: list[Tensor], ln: list[Tensor]):
+    l1, l2 = (list(ln[:4]), list(ln[4:])) if len(ln) else ([None] * 4, [None] * 4)
+    return list(wb[:6]) + l1, list(wb[6:]) + l2
+
+
+@custom_op("lgnn::isab", mutates_args=(), device_types="cuda")
+def isab(x: Tensor, ind: Tensor, wb: list[Tensor], ln: list[Tensor], ptr: Optional[Tensor],
+         rows: int, num_sets: int, heads: int, mask1: Optional[Tensor],
+         mask2: Optional[Tensor]) -> list[Tensor]:
+    """[out, h = mab1's output, mab1's ops.MAB_SAVED, mab2's ops.MAB_SAVED]"""
+    p1, p2 = _isab_params(wb, ln)
+    out, (sv1, sv2) = ops.isab_fwd(x, ind, p1, p2, ptr, rows, num_sets, heads, mask1, mask2)
+    return [out, sv2.y] + [_enc(getattr(sv, n), x.device) for sv in (sv1, sv2)
+                           for n in ops.MAB_SAVED]
+
+
+def _mab_saved_fake(x, y, C, R, heads, has_ln, mask, num_sets):
+    """ops.MAB_SAVED of a block with query input x, key input y (None: x) and R output rows."""
+    f = lambda *s: x.new_empty(*s, dtype=torch.float32)  # noqa: E731
+    none = lambda: x.new_empty(0, dtype=torch.uint8)  # noqa: E731
+    stat = (lambda: f(R)) if has_ln else none
+    proj = f(x.shape[0], 3 * C if y is None else C)
+    kv = none() if y is None else f(y.shape[0], 2 * C)
+    moff = none() if mask is None else x.new_empty(num_sets + 1, dtype=torch.int64)
+    return [proj, kv, f(R, C), f(R, heads), f(R, C), stat(), stat(), f(R, C), f(R, C), stat(),
+            stat(), moff]
+
+
+@isab.register_fake
+def _(x, ind, wb, ln, ptr, rows, num_sets, heads, mask1, mask2):
+    C = x.shape[1]
+    m = ind.shape[0]
+    h = x.new_empty(num_sets * m, C)
+    return [torch.empty_like(x), h] \
+        + _mab_saved_fake(ind, x, C, num_sets * m, heads, len(ln) > 0, mask1, num_sets) \
+        + _mab_saved_fake(x, h, C, x.shape[0], heads, len(ln) > 0, mask2, num_sets)
+
+
+@custom_op("lgnn::isab_bwd", mutates_args=(), device_types="cuda")
+def isab_bwd(dout: Tensor, x: Tensor, ind: Tensor, h: Tensor, wb: list[Tensor],
+             ln: list[Tensor], saved: list[Tensor], ptr: Optional[Tensor], rows: int,
+             num_sets: int, heads: int, mask1: Optional[Tensor], mask2: Optional[Tensor],
+             want_dx: bool) -> list[Tensor]:
+    """[dx, dind, mab1's then mab2's six weight / bias gradients, then their four LayerNorm
+    gradients each] (absent: empty)."""
+    p1, p2 = _isab_params(wb, ln)
+    n = len(ops.MAB_SAVED)
+    f1, f2 = ops.isab_forms(ptr, rows, ind.shape[0], num_sets)
+    c = lambda ps: [p.contiguous() if p is not None else None for p in ps]  # noqa: E731
+    x, ind = x.contiguous(), ind.contiguous()
+    sv1 = ops.MabSaved(ind, x, c(p1), f1, heads, mask1, *[_opt(t) for t in saved[:n]])
+    sv2 = ops.MabSaved(x, h, c(p2), f2, heads, mask2, *[_opt(t) for t in saved[n:]])
+    dx, dind, d1, d2 = ops.isab_bwd((sv1, sv2), dout, want_dx)
+    return _grad_list([dx, dind] + d1[:6] + d2[:6] + d1[6:] + d2[6:], x.device)
+
+
+@isab_bwd.register_fake
+def _(dout, x, ind, h, wb, ln, saved, ptr, rows, num_sets, heads, mask1, mask2, want_dx):
+    none = lambda: x.new_empty(0, dtype=torch.uint8)  # noqa: E731
+    return [torch.empty_like(x) if want_dx else none(), torch.empty_like(ind)] + \
+        [torch.empty_like(p) for p in wb] + \
+        ([torch.empty_like(p) for p in ln] if len(ln) else [none() for _ in range(8)])
+
+
+def _isab_setup(ctx, inputs, output):
+    x, ind, wb, ln, ptr, rows, num_sets, heads, mask1, mask2 = inputs
+    ts = [ptr, mask1, mask2]
+    ctx.present = [t is not None for t in ts]
+    ctx.counts = (len(wb), len(ln))
+    ctx.save_for_backward(*[t for t in ts if t is not None], x, ind, *wb, *ln, *output[1:])
+    ctx.meta = (rows, num_sets, heads)
+
+
+def _isab_backward(ctx, grads):
+    st = list(ctx.saved_tensors)
+    ptr, mask1, mask2 = [st.pop(0) if p else None for p in ctx.present]
+    x, ind = st.pop(0), st.pop(0)
+    nwb, nln = ctx.counts
+    wb, ln, h, saved = st[:nwb], st[nwb:nwb + nln], st[nwb + nln], st[nwb + nln + 1:]
+    rows, num_sets, heads = ctx.meta
+    g = torch.ops.lgnn.isab_bwd(grads[0], x, ind, h, wb, ln, saved, ptr, rows, num_sets, heads,
+                                mask1, mask2, ctx.needs_input_grad[0])
+    return (_opt(g[0]), g[1], list(g[2:2 + nwb]), list(g[2 + nwb:2 + nwb + nln]) if nln else [],
+            None, None, None, None, None, None)
+
+
+isab.register_autograd(_isab_backward, setup_context=_isab_setup)
+
+
+@custom_op("lgnn::set_attn", mutates_args=(), device_types="cuda")
+def set_attn(q: Tensor, k: Tensor, v: Tensor, qptr: Optional[Tensor], kptr: Optional[Tensor],
+             q_rows: int, q_shared: bool, k_rows: int, num_sets: int, heads: int,
+             mask: Optional[Tensor]) -> list[Tensor]:
+    """[out, lse, mask_off]"""
+    form = ops.AttnForm(qptr, q_rows, q_shared, kptr, k_rows, num_sets)
+    out, sv = ops.set_attn_fwd(q, k, v, form, heads, mask)
+    return [out, sv.lse, _enc(sv.moff, q.device)]
+
+
+@set_attn.register_fake
+def _(q, k, v, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask):
+    R = _mab_rows(q, qptr, q_rows, num_sets)
+    moff = q.new_empty(0, dtype=torch.uint8) if mask is None else \
+        q.new_empty(num_sets + 1, dtype=torch.int64)
+    return [q.new_empty(R, q.shape[1]), q.new_empty(R, heads), moff]
+
+
+@custom_op("lgnn::set_attn_bwd", mutates_args=(), device_types="cuda")
+def set_attn_bwd(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, out: Tensor, lse: Tensor,
+                 moff: Tensor, qptr: Optional[Tensor], kptr: Optional[Tensor], q_rows: int,
+                 q_shared: bool, k_rows: int, num_sets: int, heads: int,
+                 mask: Optional[Tensor]) -> list[Tensor]:
+    form = ops.AttnForm(qptr, q_rows, q_shared, kptr, k_rows, num_sets)
+    sv = ops.AttnSaved(ops._rows_view(q), ops._rows_view(k), ops._rows_view(v), form, heads, mask,
+                       _opt(moff), out, lse)
+    return list(ops.set_attn_bwd(sv, dout))
+
+
+@set_attn_bwd.register_fake
+def _(dout, q, k, v, out, lse, moff, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask):
+    return [q.new_empty(q.shape), k.new_empty(k.shape), v.new_empty(v.shape)]
+
+
+def _set_attn_setup(ctx, inputs, output):
+    q, k, v, qptr, kptr, q_rows, q_shared, k_rows, num_sets, heads, mask = inputs
+    ts = [qptr, kptr, mask]
+    ctx.present = [t is not None for t in ts]
+    ctx.save_for_backward(*[t for t in ts if t is not None], q, k, v, *output)
+    ctx.meta = (q_rows, q_shared, k_rows, num_sets, heads)
+
+
+def _set_attn_backward(ctx, grads):
+    st = list(ctx.saved_tensors)
+    qptr, kptr, mask = [st.pop(0) if p else None for p in ctx.present]
+    q, k, v, out, lse, moff = st
+    dq, dk, dv = torch.ops.lgnn.set_attn_bwd(grads[0], q, k, v, out, lse, moff, qptr, kptr,
+                                             *ctx.meta, mask)
+    return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+set_attn.register_autograd(_set_attn_backward, setup_context=_set_attn_setup)

@@ -1,16 +1,18 @@
 """Model registry (reference src/lesion_gnn/models/__init__.py:10,22-35: isinstance dispatch on
-the config type), restricted to the message-passing families of the hot path."""
+the config type): the message-passing families of the hot path and the SetTransformer."""
 from .base import (BaseModelConfig, BaseModule, LossType, LRSchedulerConfig, OptimizerAlgo,
                    OptimizerConfig)
 from .gcn import GCN, GCNConfig, GCNModule
 from .gat import GAT, GATConfig, GATModule
 from .gin import GIN, GINConfig, GINModule
 from .drgnet import DRGNet, DRGNetModelConfig, DRGNetModule
+from .set_transformer import SetTransformer, SetTransformerModelConfig, SetTransformerModule
 
-ModelConfig = DRGNetModelConfig | GCNConfig | GINConfig | GATConfig
+ModelConfig = DRGNetModelConfig | GCNConfig | GINConfig | GATConfig | SetTransformerModelConfig
 
 __all__ = ["GCN", "GCNConfig", "GCNModule", "GIN", "GINConfig", "GINModule", "GAT", "GATConfig",
-           "GATModule", "DRGNet", "DRGNetModelConfig", "DRGNetModule", "BaseModule",
+           "GATModule", "DRGNet", "DRGNetModelConfig", "DRGNetModule", "SetTransformer",
+           "SetTransformerModelConfig", "SetTransformerModule", "BaseModule",
            "BaseModelConfig", "OptimizerConfig", "OptimizerAlgo", "LossType", "LRSchedulerConfig",
            "ModelConfig", "get_model"]
 
@@ -24,4 +26,6 @@ def get_model(config) -> BaseModule:
         return GINModule(config)
     if isinstance(config, GATConfig):
         return GATModule(config)
+    if isinstance(config, SetTransformerModelConfig):
+        return SetTransformerModule(config)
     raise ValueError(f"Unknown model config type {type(config)}")

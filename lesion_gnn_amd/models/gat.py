@@ -1,7 +1,8 @@
 """GAT graph classifier — reference src/lesion_gnn/models/gat.py:17-97 (GAT, GATConfig,
 GATLightning), including the config field typo `hiddden_channels` (gat.py:65, used by
 configs/config.py:61). The SetTransformer readout branch (gat.py:33-43, `num_st_seed_points`)
-is out of scope (no config enables it); passing it raises.
+is not wired in (no config enables it): the aggregation exists
+(conv.SetTransformerAggregation), passing the argument still raises.
 
 forward(x, edge_index | Graph, batch) is the drop-in boundary `self.model(data.x, edge_index,
 data.batch)` (reference gat.py:92): in_proj -> L x ELU(GATConv) -> global_mean_pool -> out_proj,
@@ -41,8 +42,10 @@ class GAT(nn.Module):
         self.bf16 = precision == "bf16"
         assert all(d % heads == 0 for d in hiddden_channels)
         if num_st_seed_points is not None:
-            raise NotImplementedError("SetTransformerAggregation readout (reference gat.py:33-43)"
-                                      " is out of scope for this build")
+            raise NotImplementedError("the SetTransformerAggregation readout (reference "
+                                      "gat.py:33-43) is not wired into GAT yet: the aggregation "
+                                      "itself exists (lesion_gnn_amd.conv."
+                                      "SetTransformerAggregation)")
         if pool not in ("mean", "add"):
             raise ValueError(f"pool must be 'mean' or 'add', got {pool!r}")
         self.in_proj = nn.Linear(input_features, hiddden_channels[0])

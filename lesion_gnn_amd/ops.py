@@ -7,6 +7,9 @@
 - `gcn_stack`       the whole GCN model body as ONE autograd node: in_proj -> L x (GCNConv, ELU)
                     -> pool -> out_proj, with a fused backward chain (pool-broadcast and the
                     transposed aggregation feed the next kernel's prologue, never materialised).
+- `set_attention`   segmented multi-head attention over ragged sets; `mab` / `isab`: PyG's
+                    MultiheadAttentionBlock / InducedSetAttentionBlock as ONE autograd node each;
+                    `res_norm` (residual + activation + LayerNorm), `set_readout`
 """
 from __future__ import annotations
 
@@ -2179,3 +2182,447 @@ def cc_pool(features: torch.Tensor, cc: torch.Tensor, num_segments: int, reduce_
     if validate and int(err.item()):
         raise IndexError(f"cc_pool: {int(err.item())} labels outside [0, {num_segments})")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Set attention (setattn.hip): segmented multi-head attention over ragged sets, the residual +
+# activation + LayerNorm of PyG's MultiheadAttentionBlock, the set readout
+# ----------------------------------------------------------------------------------------------
+
+
+# Which rows of q and k / v belong to set g (lgnn_set_attn_fwd): qptr / kptr int32 [B + 1]
+# offsets (ragged rows, Batch.ptr) or None with q_rows / k_rows rows per set; q_shared: the same
+# q_rows query rows for every set (PMA's seeds, ISAB's inducing points).
+AttnForm = namedtuple("AttnForm", "qptr q_rows q_shared kptr k_rows num_sets")
+
+
+def set_attn_plan(heads: int, head_dim: int) -> None:
+    """The shapes the attention kernels take; anything else raises (no other path exists)."""
+    if heads < 1 or not 1 <= head_dim <= _lib.LGNN_SET_ATTN_MAX_D \
+            or heads * head_dim > _lib.LGNN_SET_ATTN_MAX_HD:
+        raise NotImplementedError(
+            f"set attention takes head_dim in 1..{_lib.LGNN_SET_ATTN_MAX_D} and heads * head_dim "
+            f"<= {_lib.LGNN_SET_ATTN_MAX_HD}; got heads = {heads}, head_dim = {head_dim}")
+
+
+def _rows_view(t: torch.Tensor) -> torch.Tensor:
+    """t as the kernels read a row operand: fp32 [rows, cols] with unit column stride (a column
+    block of a packed projection output stays a view)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"expected float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise ValueError("expected [rows, channels]")
+    return t if t.size(1) == 1 or t.stride(1) == 1 else t.contiguous()
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.size(0) > 1 else t.size(1)
+
+
+def attn_out_rows(form: AttnForm, q_rows_given: int) -> int:
+    return q_rows_given if form.qptr is not None else form.num_sets * form.q_rows
+
+
+def set_attn_mask_numel(form: AttnForm, heads: int, Mq: int, Mk: int):
+    """Elements of the [set][head][query][key] dropout mask, or None when both sides are ragged
+    (the size then depends on the set sizes: sum_g heads * n_g^2)."""
+    if form.qptr is None and form.kptr is None:
+        return form.num_sets * heads * form.q_rows * form.k_rows
+    if form.qptr is None:
+        return heads * form.q_rows * Mk
+    if form.kptr is None:
+        return heads * Mq * form.k_rows
+    return None
+
+
+def set_attn_mask_offsets(form: AttnForm, heads: int, dev) -> torch.Tensor:
+    """int64 [B + 1]: where each set's [head][query][key] block of the mask starts."""
+    moff = torch.empty(form.num_sets + 1, dtype=torch.int64, device=dev)
+    _lib.call("lgnn_set_attn_mask_offsets", form.qptr, form.q_rows, form.kptr, form.k_rows,
+              form.num_sets, heads, moff, _s(dev))
+    return moff
+
+
+AttnSaved = namedtuple("AttnSaved", "q k v form heads mask moff out lse")
+
+
+def _attn_args(q, k, v, form: AttnForm, heads: int, mask, moff):
+    return (q, _ld(q), k, _ld(k), v, _ld(v), form.qptr, form.q_rows, int(form.q_shared),
+            form.kptr, form.k_rows, form.num_sets, heads, q.size(1) // heads, mask, moff)
+
+
+def set_attn_fwd(q, k, v, form: AttnForm, heads: int, mask=None, moff=None):
+    """softmax(q_h k_h^T / sqrt(D)) [* mask] v_h per set and head: (out [rows, C], AttnSaved).
+    q, k, v [rows, C] fp32, column blocks of a packed projection allowed."""
+    _lib.require_gpu(q, k, v)
+    q, k, v = _rows_view(q), _rows_view(k), _rows_view(v)
+    C = q.size(1)
+    if C % heads or k.size(1) != C or v.size(1) != C:
+        raise ValueError("set attention: q, k, v must be [rows, heads * head_dim]")
+    set_attn_plan(heads, C // heads)
+    dev = q.device
+    if mask is not None and moff is None:
+        moff = set_attn_mask_offsets(form, heads, dev)
+    R = attn_out_rows(form, q.size(0))
+    out = torch.empty(R, C, dtype=torch.float32, device=dev)
+    lse = torch.empty(R, heads, dtype=torch.float32, device=dev)
+    _lib.call("lgnn_set_attn_fwd", *_attn_args(q, k, v, form, heads, mask, moff), out, lse,
+              _s(dev))
+    return out, AttnSaved(q, k, v, form, heads, mask, moff, out, lse)
+
+
+def set_attn_bwd(sv: AttnSaved, dout, dq=None, dk=None, dv=None, jobs: list | None = None):
+    """(dq, dk, dv); given dq / dk / dv (views with unit column stride, e.g. column blocks of one
+    packed gradient) are written in place. Shared queries: the per-set dq rows are summed over the
+    sets in fixed order (a reduce_multi job: appended to `jobs`, else run here)."""
+    q, k, v, form = sv.q, sv.k, sv.v, sv.form
+    dev = q.device
+    dout = _f32c(dout)
+    C = q.size(1)
+    S, B = form.q_rows, form.num_sets
+    dq_out = dq if dq is not None else torch.empty(q.size(0), C, dtype=torch.float32, device=dev)
+    dk = dk if dk is not None else torch.empty(k.size(0), C, dtype=torch.float32, device=dev)
+    dv = dv if dv is not None else torch.empty(v.size(0), C, dtype=torch.float32, device=dev)
+    dq_k = torch.empty(B * S, C, dtype=torch.float32, device=dev) if form.q_shared else dq_out
+    _lib.call("lgnn_set_attn_bwd", *_attn_args(q, k, v, form, sv.heads, sv.mask, sv.moff),
+              sv.out, dout, sv.lse, dq_k, _ld(dq_k), dk, _ld(dk), dv, _ld(dv), _s(dev))
+    if form.q_shared:
+        if not dq_out.is_contiguous():
+            raise ValueError("shared-query dq must be contiguous")
+        if B == 0:
+            dq_out.zero_()
+        else:
+            job = [(dq_k, B, S * C, dq_out)]
+            if jobs is not None:
+                jobs.extend(job)
+            else:
+                reduce_multi(job, dev)
+    return dq_out, dk, dv
+
+
+class _SetAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, form, heads, mask):
+        out, saved = set_attn_fwd(q, k, v, form, heads, mask)
+        _save(ctx, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        return (*set_attn_bwd(_load(ctx), dout), None, None, None)
+
+
+def set_attention(q, k, v, form: AttnForm, heads: int, mask=None):
+    """Segmented multi-head attention as one autograd node (the blocks of conv.py run it inside
+    ops.mab, with their projections)."""
+    if _compiling():
+        return torch.ops.lgnn.set_attn(q, k, v, form.qptr, form.kptr, int(form.q_rows),
+                                       bool(form.q_shared), int(form.k_rows), form.num_sets,
+                                       int(heads), mask)[0]
+    return _SetAttn.apply(q, k, v, form, heads, mask)
+
+
+NormSaved = namedtuple("NormSaved", "a a_rows b act gamma mean rstd")
+
+
+def res_norm_fwd(a, a_rows: int, b, act: int, gamma=None, beta=None, eps: float = 1e-5):
+    """y = LN(a + act(b)) (a None: LN(act(b)); gamma None: no LayerNorm): (y, NormSaved).
+    a_rows > 0: a is [a_rows, C], broadcast over the sets (row r reads a[r % a_rows])."""
+    _lib.require_gpu(a, b, gamma)
+    b = _f32c(b)
+    a = _f32c(a) if a is not None else None
+    M, C = b.shape
+    dev = b.device
+    y = torch.empty_like(b)
+    mean = rstd = None
+    if gamma is not None:
+        gamma, beta = _f32c(gamma), _f32c(beta)
+        mean = torch.empty(M, dtype=torch.float32, device=dev)
+        rstd = torch.empty(M, dtype=torch.float32, device=dev)
+    _lib.call("lgnn_res_norm_fwd", a, int(a_rows), b, int(act), gamma, beta, float(eps), M, C, y,
+              mean, rstd, _s(dev))
+    return y, NormSaved(a, int(a_rows), b, int(act), gamma, mean, rstd)
+
+
+def res_norm_bwd(sv: NormSaved, dy, want_da: bool = True, want_db: bool = True,
+                 jobs: list | None = None):
+    """(da, db, dgamma, dbeta), None where not asked for / absent. da of a broadcast a and the
+    affine gradients are fixed-order sums (reduce_multi jobs: appended to `jobs`, else run)."""
+    dy = _f32c(dy)
+    M, C = sv.b.shape
+    dev = sv.b.device
+    want_da = want_da and sv.a is not None
+    da_rows = torch.empty(M, C, dtype=torch.float32, device=dev) if want_da else None
+    db = torch.empty(M, C, dtype=torch.float32, device=dev) if want_db else None
+    P = _lib.load().lgnn_res_norm_bwd_partials(M)
+    part = torch.empty(P * 2 * C, dtype=torch.float32, device=dev) \
+        if sv.gamma is not None else None
+    _lib.call("lgnn_res_norm_bwd", sv.a, sv.a_rows, sv.b, sv.act, sv.gamma, M, C, sv.mean,
+              sv.rstd, dy, da_rows, db, part, P, _s(dev))
+    local = []
+    da = da_rows
+    if want_da and sv.a_rows > 0:
+        da = torch.empty(sv.a_rows, C, dtype=torch.float32, device=dev)
+        if M == 0:
+            da.zero_()
+        else:
+            local.append((da_rows, M // sv.a_rows, sv.a_rows * C, da))
+    dgamma = dbeta = None
+    if part is not None:
+        dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+        local += [(part[:P * C], P, C, dgamma), (part[P * C:], P, C, dbeta)]
+    if jobs is not None:
+        jobs.extend(local)
+    else:
+        reduce_multi(local, dev)
+    return da, db, dgamma, dbeta
+
+
+class _ResNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, act, gamma, beta, a_rows, eps):
+        y, saved = res_norm_fwd(a, a_rows, b, act, gamma, beta, eps)
+        _save(ctx, saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        need = ctx.needs_input_grad
+        da, db, dg, dbt = res_norm_bwd(_load(ctx), dy, need[0], need[1])
+        return da, db, None, dg, dbt, None, None
+
+
+def res_norm(a, b, act: int = _lib.LGNN_ACT_NONE, gamma=None, beta=None, a_rows: int = 0,
+             eps: float = 1e-5):
+    """y = LN(a + act(b)); a None: LN(act(b)); gamma None: no LayerNorm."""
+    if _compiling():
+        return torch.ops.lgnn.res_norm(a, b, int(act), gamma, beta, int(a_rows), float(eps))[0]
+    return _ResNorm.apply(a, b, act, gamma, beta, a_rows, eps)
+
+
+def set_readout_fwd(x, gptr, num_sets: int, rows: int, mean: bool):
+    _lib.require_gpu(x)
+    x = _f32c(x)
+    C = x.size(1)
+    out = torch.empty(num_sets, C if mean else rows * C, dtype=torch.float32, device=x.device)
+    _lib.call("lgnn_set_readout_fwd", x, gptr, num_sets, int(rows), C, int(mean), out,
+              _s(x.device))
+    return out
+
+
+def set_readout_bwd(dout, gptr, num_sets: int, rows: int, C: int, mean: bool):
+    dout = _f32c(dout)
+    dx = torch.empty(num_sets * rows, C, dtype=torch.float32, device=dout.device)
+    _lib.call("lgnn_set_readout_bwd", dout, gptr, num_sets, int(rows), C, int(mean), dx,
+              _s(dout.device))
+    return dx
+
+
+class _SetReadout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gptr, num_sets, rows, mean):
+        ctx.gptr, ctx.meta = gptr, (num_sets, rows, x.size(1), mean)
+        return set_readout_fwd(x, gptr, num_sets, rows, mean)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return set_readout_bwd(dout, ctx.gptr, *ctx.meta), None, None, None, None
+
+
+def set_readout(x, gptr, num_sets: int, rows: int, mean: bool):
+    """[num_sets * rows, C] -> [num_sets, C] (mean over a set's rows) or [num_sets, rows * C];
+    with gptr (the input sets' offsets) the rows of an empty set are zero."""
+    if _compiling():
+        return torch.ops.lgnn.set_readout(x, gptr, num_sets, int(rows), bool(mean))
+    return _SetReadout.apply(x, gptr, num_sets, rows, mean)
+
+
+def _add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a + b on lgnn_add (two gradient paths meeting at a block's input)."""
+    y = torch.empty_like(a)
+    _lib.call("lgnn_add", a, b, y, a.numel(), _s(a.device))
+    return y
+
+
+def _mab_lin_fwd(x, W, b):
+    """x W^T + b on the existing linears, chosen as linear_auto chooses: the tile kernels where
+    the shape is theirs, else the split-3 dense GEMM (any M >= 0, any width)."""
+    if fast_shape(W.size(1), W.size(0)):
+        return linear_fwd(x, W, b, _lib.LGNN_ACT_NONE)
+    return dense_mm(x, dense_planes(W, False, False), W.size(0), b, False)
+
+
+def _mab_lin_bwd(x, W, dy, want_dx: bool, jobs: list, copies: list, dW_out=None, db_out=None):
+    """(dx or None, dW, db) of _mab_lin_fwd; the slab reductions go to `jobs`, retargeted at
+    dW_out / db_out (row blocks of in_proj_weight.grad / in_proj_bias.grad) when given."""
+    N, K = W.shape
+    local: list = []
+    if fast_shape(K, N):
+        dx, dW, db = linear_bwd(_lib.LGNN_GRAD_DIRECT, dy, H=None, act=_lib.LGNN_ACT_NONE, X=x,
+                                W=W, want_dx=want_dx, want_db=True, reducer=local)
+    else:
+        dW, db = dense_wgrad(dy, x, False, want_db=True, reducer=local)
+        dx = dense_mm(dy, dense_planes(W, True, False), K, None, False) if want_dx else None
+    if dW_out is not None:
+        if local[0][3].shape == dW_out.shape:  # the reduction writes the row block itself
+            local = [(*local[0][:3], dW_out), (*local[1][:3], db_out)]
+        else:  # an odd width the GEMM padded: copied after the reduction
+            copies += [(dW_out, dW), (db_out, db)]
+        dW, db = dW_out, db_out
+    jobs.extend(local)
+    return dx, dW, db
+
+
+# params: [in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, lin.weight, lin.bias,
+# layer_norm1.weight, layer_norm1.bias, layer_norm2.weight, layer_norm2.bias] (the last four None
+# without LayerNorm). y None: self attention (mab(x, x): one packed q/k/v projection).
+MAB_SAVED = ("proj", "kv", "o", "lse", "a", "mean1", "rstd1", "u1", "t", "mean2", "rstd2", "moff")
+MabSaved = namedtuple("MabSaved", ("x", "y", "params", "form", "heads", "mask") + MAB_SAVED)
+
+
+def mab_fwd(x, y, params: list, form: AttnForm, heads: int, mask=None):
+    """PyG 2.5.1 MultiheadAttentionBlock.forward(x, y) on ragged sets: (out, MabSaved)."""
+    _lib.require_gpu(x, y, params[0])
+    x = _f32c(x)
+    y = _f32c(y) if y is not None else None
+    params = [_f32c(p) if p is not None else None for p in params]
+    Win, bin_, Wo, bo, Wl, bl, g1, b1, g2, b2 = params
+    C = Win.size(1)
+    set_attn_plan(heads, C // heads)
+    if y is None:
+        proj, kv = _mab_lin_fwd(x, Win, bin_), None
+        q, k, v = proj[:, :C], proj[:, C:2 * C], proj[:, 2 * C:]
+    else:
+        proj = _mab_lin_fwd(x, Win[:C], bin_[:C])
+        kv = _mab_lin_fwd(y, Win[C:], bin_[C:])
+        q, k, v = proj, kv[:, :C], kv[:, C:]
+    o, asv = set_attn_fwd(q, k, v, form, heads, mask)
+    a = _mab_lin_fwd(o, Wo, bo)
+    u1, n1 = res_norm_fwd(x, form.q_rows if form.q_shared else 0, a, _lib.LGNN_ACT_NONE, g1, b1)
+    t = _mab_lin_fwd(u1, Wl, bl)
+    u2, n2 = res_norm_fwd(u1, 0, t, _lib.LGNN_ACT_RELU, g2, b2)
+    return u2, MabSaved(x, y, params, form, heads, mask, proj, kv, o, asv.lse, a, n1.mean,
+                        n1.rstd, u1, t, n2.mean, n2.rstd, asv.moff)
+
+
+def mab_bwd(sv: MabSaved, dout, want_dx: bool = True, want_dy: bool = True):
+    """(dx or None, dy or None, [the gradients of params, None where the parameter is None])."""
+    x, y, form, heads = sv.x, sv.y, sv.form, sv.heads
+    Win, bin_, Wo, bo, Wl, bl, g1, b1, g2, b2 = sv.params
+    C = Win.size(1)
+    dev = x.device
+    jobs: list = []
+    copies: list = []
+    n2 = NormSaved(sv.u1, 0, sv.t, _lib.LGNN_ACT_RELU, g2, sv.mean2, sv.rstd2)
+    du1_res, dt, dg2, db2 = res_norm_bwd(n2, dout, True, True, jobs)
+    du1_lin, dWl, dbl = _mab_lin_bwd(sv.u1, Wl, dt, True, jobs, copies)
+    du1 = _add(du1_res, du1_lin)
+    n1 = NormSaved(x, form.q_rows if form.q_shared else 0, sv.a, _lib.LGNN_ACT_NONE, g1, sv.mean1,
+                   sv.rstd1)
+    dx_res, da, dg1, db1 = res_norm_bwd(n1, du1, want_dx, True, jobs)
+    do, dWo, dbo = _mab_lin_bwd(sv.o, Wo, da, True, jobs, copies)
+    dWin = torch.empty_like(Win)
+    dbin = torch.empty_like(bin_)
+    if y is None:
+        q, k, v = sv.proj[:, :C], sv.proj[:, C:2 * C], sv.proj[:, 2 * C:]
+        dproj = torch.empty_like(sv.proj)
+        dq, dk, dv = dproj[:, :C], dproj[:, C:2 * C], dproj[:, 2 * C:]
+    else:
+        q, k, v = sv.proj, sv.kv[:, :C], sv.kv[:, C:]
+        dproj, dkv = torch.empty_like(sv.proj), torch.empty_like(sv.kv)
+        dq, dk, dv = dproj, dkv[:, :C], dkv[:, C:]
+    asv = AttnSaved(q, k, v, form, heads, sv.mask, sv.moff, sv.o, sv.lse)
+    set_attn_bwd(asv, do, dq, dk, dv, jobs)
+    if form.q_shared and jobs and jobs[-1][3] is dq:
+        # the q projection's backward reads the summed dq: run what is queued so far
+        reduce_multi(jobs, dev)
+        jobs = []
+    dy = None
+    if y is None:
+        dx_lin, _, _ = _mab_lin_bwd(x, Win, dproj, want_dx, jobs, copies, dWin, dbin)
+    else:
+        dx_lin, _, _ = _mab_lin_bwd(x, Win[:C], dproj, want_dx, jobs, copies, dWin[:C], dbin[:C])
+        dy, _, _ = _mab_lin_bwd(y, Win[C:], dkv, want_dy, jobs, copies, dWin[C:], dbin[C:])
+    reduce_multi(jobs, dev)
+    for dst, src in copies:
+        dst.copy_(src)
+    dx = _add(dx_res, dx_lin) if want_dx else None
+    return dx, dy, [dWin, dbin, dWo, dbo, dWl, dbl, dg1, db1, dg2, db2]
+
+
+class _Mab(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, form, heads, mask, *params):
+        out, saved = mab_fwd(x, y, list(params), form, heads, mask)
+        _save(ctx, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        need = ctx.needs_input_grad
+        dx, dy, dps = mab_bwd(_load(ctx), dout, need[0], need[1])
+        return (dx, dy, None, None, None, *dps)
+
+
+def mab(x, y, params: list, form: AttnForm, heads: int, mask=None):
+    """MultiheadAttentionBlock(x, y) as ONE autograd node: the q / k / v projections (one packed
+    GEMM when y is None, i.e. y is x), the segmented attention, out_proj, the residuals, the ReLU
+    Linear and both LayerNorms. in_proj_weight's gradient comes out as one [3C, C] tensor."""
+    if _compiling():
+        return torch.ops.lgnn.mab(x, y, list(params[:6]), list(params[6:]) if params[6] is not None
+                                  else [], form.qptr, form.kptr, int(form.q_rows),
+                                  bool(form.q_shared), int(form.k_rows), form.num_sets,
+                                  int(heads), mask)[0]
+    return _Mab.apply(x, y, form, heads, mask, *params)
+
+
+def isab_forms(ptr, rows: int, m: int, num_sets: int):
+    """The two attention forms of an InducedSetAttentionBlock over sets laid out by (ptr | rows):
+    the m inducing rows query each set; each set's rows query its m induced rows."""
+    return (AttnForm(None, m, True, ptr, rows, num_sets),
+            AttnForm(ptr, rows, False, None, m, num_sets))
+
+
+def isab_fwd(x, ind, params1: list, params2: list, ptr, rows: int, num_sets: int, heads: int,
+             mask1=None, mask2=None):
+    """PyG InducedSetAttentionBlock: mab2(x, mab1(ind, x)): (out, (MabSaved, MabSaved))."""
+    f1, f2 = isab_forms(ptr, rows, ind.size(0), num_sets)
+    h, sv1 = mab_fwd(ind, x, params1, f1, heads, mask1)
+    out, sv2 = mab_fwd(x, h, params2, f2, heads, mask2)
+    return out, (sv1, sv2)
+
+
+def isab_bwd(svs, dout, want_dx: bool = True):
+    """(dx or None, dind, grads of params1, grads of params2). x feeds both blocks (mab1's keys,
+    mab2's queries): its two gradients meet in lgnn_add."""
+    sv1, sv2 = svs
+    dx2, dh, dps2 = mab_bwd(sv2, dout, want_dx, True)
+    dind, dx1, dps1 = mab_bwd(sv1, dh, True, want_dx)
+    return (_add(dx2, dx1) if want_dx else None), dind, dps1, dps2
+
+
+class _Isab(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ind, ptr, rows, num_sets, heads, mask1, mask2, *params):
+        out, saved = isab_fwd(x, ind, list(params[:10]), list(params[10:]), ptr, rows, num_sets,
+                              heads, mask1, mask2)
+        _save(ctx, saved)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, dind, dps1, dps2 = isab_bwd(_load(ctx), dout, ctx.needs_input_grad[0])
+        return (dx, dind, None, None, None, None, None, None, *dps1, *dps2)
+
+
+def isab(x, ind, params1: list, params2: list, ptr, rows: int, num_sets: int, heads: int,
+         mask1=None, mask2=None):
+    """InducedSetAttentionBlock as ONE autograd node (x is read by both of its attention blocks;
+    inside one node the two input gradients are summed by a HIP kernel)."""
+    if _compiling():
+        ln = params1[6] is not None
+        return torch.ops.lgnn.isab(x, ind, list(params1[:6]) + list(params2[:6]),
+                                   (list(params1[6:]) + list(params2[6:])) if ln else [], ptr,
+                                   int(rows), num_sets, int(heads), mask1, mask2)[0]
+    return _Isab.apply(x, ind, ptr, rows, num_sets, heads, mask1, mask2, *params1, *params2)
