@@ -1035,6 +1035,97 @@ int lgnn_set_readout_bwd(const float* dout, const int32_t* gptr, int64_t num_set
  * (the residual's and the projection's: autograd's AccumulateGrad add). */
 int lgnn_add(const float* a, const float* b, float* y, int64_t n, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PointNet++ (reference src/lesion_gnn/models/pointnet.py; PyG 2.5.1 PointNetConv, fps, radius,
+ * global_max_pool; torch_cluster 1.6.3). The entries are additions: every earlier signature is
+ * unchanged, so the ABI version stays.
+ *
+ * Geometry conventions as lgnn_knn_graph / lgnn_radius_graph: positions fp64 [rows][dims], dims 2
+ * or 3 (fp32 positions widen exactly); squared distances fp64 with each operation rounded on its
+ * own, so every selection is bit-exact against a float64 restatement; ptr int32 graph offsets;
+ * nothing is allocated inside a call.
+ *
+ * lgnn_fps: farthest point sampling of every graph in one launch (torch_cluster.fps). ptr [B+1]
+ *   the graphs' point offsets, optr [B+1] their output offsets (m_g = optr[g+1] - optr[g] picks,
+ *   0 <= m_g <= n_g), start [B] the local index of each graph's first pick (in [0, n_g); ignored
+ *   for an empty graph). idx [num_out = optr[B]] int64: global point indices in selection order.
+ *   After each pick p, d[i] = min(d[i], |p_i - p_p|^2); the next pick is the argmax of d, lowest
+ *   index on ties (all distinct positions taken: d is all zero and the graph's first point
+ *   repeats, as torch_cluster does). One workgroup per graph; graphs of up to LGNN_FPS_CAPACITY
+ *   points keep positions and distances in registers, larger ones use the workspace
+ *   (lgnn_fps_workspace_bytes(N)).
+ *
+ * lgnn_radius_pairs_count / lgnn_radius_pairs: torch_cluster.radius(x, y, r, batch_x, batch_y,
+ *   max_num_neighbors) — the bipartite form of lgnn_radius_graph: for every query y_i, walk the
+ *   candidates x_j of its graph (ptr_x / ptr_y: the two sets' graph offsets) in index order and
+ *   take j when |y_i - x_j|^2 < r * r, until max_num_neighbors are taken. pairs [2][E] int64 =
+ *   (query i, candidate j), grouped by i, j ascending. _count leaves the int64 row offsets
+ *   [Ny + 1] at the start of the workspace (lgnn_radius_pairs_workspace_bytes(Ny)); E is its last
+ *   entry (the one host read).
+ * lgnn_pairs_transpose: the candidate-grouped view of such a pair list: tptr [Nx + 1] int64 and
+ *   perm [E] int64 with perm[tptr[j] .. tptr[j+1]) = the pairs whose candidate is j, ascending
+ *   (count, scan, place by rank; no atomics). col = pairs + E, rowoff = the row offsets above.
+ *   workspace: lgnn_pairs_transpose_workspace_bytes(Nx).
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_FPS_CAPACITY 1024
+size_t lgnn_fps_workspace_bytes(int64_t num_nodes);
+int lgnn_fps(const double* pos, int64_t num_nodes, int dims, const int32_t* ptr,
+             const int32_t* optr, const int64_t* start, int64_t num_graphs, int64_t* idx,
+             int64_t num_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t lgnn_radius_pairs_workspace_bytes(int64_t num_queries);
+int lgnn_radius_pairs_count(const double* x, int64_t num_x, const double* y, int64_t num_y,
+                            int dims, const int32_t* ptr_x, const int32_t* ptr_y,
+                            int64_t num_graphs, double r, int max_num_neighbors, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int lgnn_radius_pairs(const double* x, int64_t num_x, const double* y, int64_t num_y, int dims,
+                      const int32_t* ptr_x, const int32_t* ptr_y, int64_t num_graphs, double r,
+                      int max_num_neighbors, int64_t* pairs, int64_t num_pairs,
+                      const void* workspace, size_t workspace_bytes, void* stream);
+size_t lgnn_pairs_transpose_workspace_bytes(int64_t num_candidates);
+int lgnn_pairs_transpose(const int64_t* col, const int64_t* rowoff, int64_t num_y,
+                         int64_t num_pairs, const int32_t* ptr_x, const int32_t* ptr_y,
+                         int64_t num_graphs, int64_t num_x, int64_t* tptr, int64_t* perm,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* PointNetConv's per-edge MLP input without a per-edge GEMM: with W1 = [Wx | Wp],
+ *   cat[x_j, pos_j - pos_i] W1^T + b1 = U[j] - V[i],  U = cat[x, pos] W1^T + b1,  V = pos_i Wp^T.
+ * lgnn_edge_sub_fwd: Z [E][C] = U[col[e]] - V[row[e]] and sums [2C] fp64 = (sum z, sum z^2) over
+ *   the E rows, as lgnn_bn_stats leaves them (same partials, same fixed-order reduction), in one
+ *   pass; workspace lgnn_bn_workspace_bytes(E, C). C % 4 == 0.
+ * lgnn_segment_sum: out [S][C] = sign * sum_{k in [ptr[s], ptr[s+1])} X[perm ? perm[k] : k], fp32
+ *   in ascending k — the backward of the above: dV = it(dZ, rowoff, NULL, -1), dU = it(dZ, tptr,
+ *   perm, +1). Every output row is written; no atomics. C % 4 == 0.
+ * lgnn_segment_max_fwd: out [S][C] = max over rows [ptr[s], ptr[s+1]) of X, arg [S][C] int32 the
+ *   row that gave it (lowest on ties); an empty segment gives 0 and arg -1. PointNetConv's
+ *   aggr='max' (segments = centroids, ptr = the pair row offsets) and global_max_pool (segments =
+ *   graphs). Any C; fewer than 2^31 rows.
+ * lgnn_segment_max_bwd: dX[e][c] = arg[seg(e)][c] == e ? dout[seg(e)][c] : 0 for every row of
+ *   every segment (the segments tile X's rows: no memset, no scatter). */
+int lgnn_edge_sub_fwd(const float* U, const float* V, const int64_t* row, const int64_t* col,
+                      int64_t num_edges, int C, float* Z, double* sums, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int lgnn_segment_sum(const float* X, const int64_t* ptr, const int64_t* perm,
+                     int64_t num_segments, int C, float sign, float* out, void* stream);
+int lgnn_segment_max_fwd(const float* X, const int64_t* ptr, int64_t num_segments, int C,
+                         float* out, int32_t* arg, void* stream);
+int lgnn_segment_max_bwd(const float* dout, const int32_t* arg, const int64_t* ptr,
+                         int64_t num_segments, int C, float* dX, void* stream);
+
+/* lgnn_bn_act / lgnn_bn_bwd_stats / lgnn_bn_bwd_apply with the activation as an argument:
+ * LGNN_ACT_ELU (what those entries compute) or LGNN_ACT_RELU (PyG MLP's default act: the
+ * PointNet++ MLPs). With scale = 1, shift = 0 and training = 0 they are act(Z) * mask and its
+ * backward (an MLP layer without a norm). lgnn_bn_stats / lgnn_bn_finalize serve both. */
+int lgnn_bn_act_a(const float* Z, int64_t M, int N, const float* scale, const float* shift,
+                  const float* mask, int act, float* A, void* stream);
+int lgnn_bn_bwd_stats_a(const float* dA, const float* Z, const float* mask, int64_t M, int N,
+                        const float* scale, const float* shift, const float* mean,
+                        const float* invstd, int act, double* sums, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int lgnn_bn_bwd_apply_a(const float* dA, const float* Z, const float* mask, int64_t M, int N,
+                        const float* scale, const float* shift, const float* mean,
+                        const float* invstd, int act, const double* sums, double count,
+                        int training, float* dZ, float* dgamma, float* dbeta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

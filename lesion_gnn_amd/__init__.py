@@ -7,19 +7,21 @@ include/lgnn.h). GPU only — there is no CPU fallback.
 """
 from . import _lib
 from . import library  # noqa: F401  (registers the lgnn:: custom ops for torch.compile)
-from .conv import (GCNConv, GraphConv, SetTransformerAggregation, global_add_pool,
-                   global_mean_pool)
+from .cluster import fps, radius
+from .conv import (GCNConv, GraphConv, PointNetConv, SetTransformerAggregation, global_add_pool,
+                   global_max_pool, global_mean_pool)
 from .graph import Graph
 from .knn import KNNGraph, knn_graph
 from .metrics import GradingMetrics
 from .transforms import GaussianDistance, SaveAs, gaussian_distance
-from .models import (GCN, GCNConfig, SetTransformer, SetTransformerModelConfig,
-                     get_model)
+from .models import (GCN, GCNConfig, PointNet, PointNetModelConfig, SetTransformer,
+                     SetTransformerModelConfig, get_model)
 
 __all__ = ["GCN", "GCNConfig", "GCNConv", "GaussianDistance", "GradingMetrics", "Graph",
-           "GraphConv", "KNNGraph", "SaveAs", "SetTransformer", "SetTransformerAggregation",
-           "SetTransformerModelConfig", "gaussian_distance", "get_model", "global_mean_pool",
-           "global_add_pool", "knn_graph", "load_library"]
+           "GraphConv", "KNNGraph", "PointNet", "PointNetConv", "PointNetModelConfig", "SaveAs",
+           "SetTransformer", "SetTransformerAggregation", "SetTransformerModelConfig", "fps",
+           "gaussian_distance", "get_model", "global_mean_pool", "global_add_pool",
+           "global_max_pool", "knn_graph", "load_library", "radius"]
 
 
 def load_library():

@@ -6,6 +6,7 @@ GINConv  — PyG GINConv(nn, eps=0): keys `nn.*`, `eps` (reference gin.py:23)
 GraphConv — PyG GraphConv(in, out): keys `lin_rel.*`, `lin_root.weight` (DRGNet,
            reference models/drgnet.py:30-33,55)
 global_mean_pool / global_add_pool — reference gin.py:33 / gat.py:56 (+ add)
+PointNetConv, DenseMLP (PyG MLP with ReLU), global_max_pool — reference models/pointnet.py
 """
 from __future__ import annotations
 
@@ -222,10 +223,128 @@ def global_add_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = Non
     return ops.segment_pool(x, g, mean=False)
 
 
+def global_max_pool(x: torch.Tensor, batch: torch.Tensor, size: int | None = None,
+                    graph: Graph | None = None) -> torch.Tensor:
+    """PyG global_max_pool; a graph without nodes gives a zero row (PyG's scatter fill)."""
+    g = graph if graph is not None else _pool_graph(x, batch, size)
+    return ops.segment_max(x, g.gptr.to(torch.int64), g.num_graphs)
+
+
 def _pool_graph(x: torch.Tensor, batch: torch.Tensor, size: int | None) -> Graph:
     _lib.require_gpu(x, batch)
     empty = torch.empty(2, 0, dtype=torch.int64, device=x.device)
     return Graph(empty, x.size(0), batch, size)
+
+
+# ----------------------------------------------------------------------------------------------
+# PointNet++: PyG 2.5.1 MLP (act="relu", norm="batch_norm" or None, plain_last=True) and
+# PointNetConv(local_nn, aggr="max") as the reference's SAModule / GlobalSAModule use them.
+# ----------------------------------------------------------------------------------------------
+
+
+class DenseMLP(nn.Module):
+    """PyG MLP(channel_list, dropout=p, act="relu", norm="batch_norm" | None, plain_last=True) for
+    any channel list: every layer but the last is Linear -> BatchNorm -> ReLU -> dropout, the
+    last a plain Linear. Keys `lins.{i}.{weight,bias}`, `norms.{i}.module.*` (norm=None: no norm
+    keys, as PyG's Identity entries). The Linears run on the dense GEMMs (ops.linear_auto), norm +
+    ReLU + dropout mask in one launch (ops.bn_act_rows). dropout: one probability or one per
+    hidden layer."""
+
+    def __init__(self, channel_list: list[int], dropout: float | list[float] = 0.0,
+                 norm: str | None = "batch_norm"):
+        super().__init__()
+        if len(channel_list) < 2:
+            raise ValueError("channel_list needs at least an input and an output width")
+        if norm not in ("batch_norm", None):
+            raise NotImplementedError(f"norm={norm!r}: only 'batch_norm' and None")
+        hidden = len(channel_list) - 2
+        if isinstance(dropout, (int, float)):
+            dropout = [float(dropout)] * hidden
+        if len(dropout) != hidden:
+            raise ValueError("one dropout probability per hidden layer")
+        self.channel_list = list(channel_list)
+        self.dropout = [float(p) for p in dropout]
+        self.lins = nn.ModuleList([nn.Linear(a, b) for a, b in
+                                   zip(channel_list[:-1], channel_list[1:])])
+        self.norms = nn.ModuleList([BatchNorm(c) if norm else nn.Identity()
+                                    for c in channel_list[1:-1]])
+
+    def mask_shapes(self, rows: int) -> list:
+        """The shape of each hidden layer's dropout mask over `rows` rows (layers with p = 0
+        included: their entry is not drawn)."""
+        return [(rows, c) for c in self.channel_list[1:-1]]
+
+    def forward(self, x: torch.Tensor | None, masks: list | None = None,
+                z0: torch.Tensor | None = None, sums0: torch.Tensor | None = None
+                ) -> torch.Tensor:
+        """masks: per hidden layer its dropout keep-mask (or None), drawn by the owning model —
+        without them an active dropout draws from the per-device generator. z0 (with sums0, its
+        BatchNorm column sums): the first Linear's output when the caller computed it
+        (PointNetConv's split first layer); x is then unused."""
+        last = len(self.lins) - 1
+        for i, lin in enumerate(self.lins):
+            z = z0 if i == 0 and z0 is not None else ops.linear_auto(x, lin.weight, lin.bias)
+            if i == last:
+                return z
+            p = self.dropout[i]
+            mask = masks[i] if masks is not None else None
+            if mask is None and p > 0.0 and self.training:
+                mask = dropout.masks(dropout.global_state(z.device), [tuple(z.shape)], p)[0]
+            norm = self.norms[i]
+            x = ops.bn_act_rows(z, norm.module if isinstance(norm, BatchNorm) else None,
+                                self.training, _lib.LGNN_ACT_RELU,
+                                mask if self.training else None,
+                                sums0 if i == 0 and z0 is not None else None)
+
+
+class PointNetConv(nn.Module):
+    """PyG PointNetConv(local_nn, global_nn=None, add_self_loops=False), aggr='max':
+    out_i = max_{j in N(i)} local_nn(cat[x_j, pos_j - pos_i]), 0 where N(i) is empty. Keys
+    `local_nn.*`.
+
+    local_nn's first Linear is never applied per edge: with W1 = [Wx | Wp],
+    cat[x_j, pos_j - pos_i] W1^T + b1 = U[j] - V[i] for U = cat[x, pos] W1^T + b1 (one row per
+    point) and V = pos_dst Wp^T (one row per centroid); the per-edge rows are their gathered
+    difference (ops.edge_sub), and dW1, db1, dx come from the node-level dU and dV. The rest of
+    local_nn runs over the E rows, then the max over each centroid's rows (ops.segment_max).
+
+    forward(x, pos, edge_index): x = the points' features or (x, x_dst) (x_dst is unused without
+    a global_nn), pos = (pos, pos_dst), edge_index = a cluster.PairGraph (radius_sets) or PyG's
+    [2, E] = [point j; centroid i] sorted by i, then j."""
+
+    def __init__(self, local_nn: DenseMLP | None = None, global_nn: nn.Module | None = None,
+                 add_self_loops: bool = False):
+        super().__init__()
+        if global_nn is not None:
+            raise NotImplementedError("PointNetConv: global_nn is not supported (the reference "
+                                      "passes none)")
+        if add_self_loops:
+            raise NotImplementedError("PointNetConv: add_self_loops=True is not supported (the "
+                                      "reference's SAModule passes False)")
+        if not isinstance(local_nn, DenseMLP):
+            raise NotImplementedError("PointNetConv: local_nn must be a conv.DenseMLP")
+        self.local_nn = local_nn
+
+    def forward(self, x, pos, edge_index) -> torch.Tensor:
+        from .cluster import PairGraph
+
+        x = x[0] if isinstance(x, (tuple, list)) else x
+        if x is None:
+            raise NotImplementedError("PointNetConv: x=None (positions only) is not supported")
+        pos, pos_dst = pos if isinstance(pos, (tuple, list)) else (pos, pos)
+        _lib.require_gpu(x, pos, pos_dst)
+        pg = edge_index if isinstance(edge_index, PairGraph) else \
+            PairGraph.from_edge_index(edge_index, x.size(0), pos_dst.size(0))
+        lin = self.local_nn.lins[0]
+        dims = pos.size(1)
+        if lin.in_features != x.size(1) + dims:
+            raise ValueError("local_nn's input width must be x's channels + pos's dimension")
+        pos, pos_dst = pos.to(x.dtype), pos_dst.to(x.dtype)
+        U = ops.linear_auto(torch.cat([x, pos], dim=1), lin.weight, lin.bias)
+        V = ops.linear_auto(pos_dst, lin.weight[:, x.size(1):])
+        z, sums = ops.edge_sub(U, V, pg)
+        msg = self.local_nn(None, z0=z, sums0=sums)
+        return ops.segment_max(msg, pg.rowoff, pg.num_queries)
 
 
 class SortAggregation(nn.Module):

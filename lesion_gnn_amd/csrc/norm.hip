@@ -29,9 +29,23 @@ __device__ __forceinline__ f32x4 ld4c(const float* p, int c, int N) {
   return c < N ? ld4(p + c) : f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// The activation after the BatchNorm, a template argument of the kernels below: LGNN_ACT_ELU (the
+// GIN MLP) or LGNN_ACT_RELU (PyG MLP's default act, the PointNet++ MLPs).
+template <int ACT>
+__device__ __forceinline__ float act_f(float zn) {
+  if constexpr (ACT == LGNN_ACT_ELU) return elu_f(zn);
+  return fmaxf(zn, 0.f);
+}
+// act'(zn) for zn = z * scale + shift (ReLU: 1 above 0, else 0, as torch's threshold_backward)
+template <int ACT>
+__device__ __forceinline__ float bn_act_grad(float z, float sc, float sh) {
+  if constexpr (ACT == LGNN_ACT_ELU) return bn_elu_grad(z, sc, sh);
+  return fmaf(z, sc, sh) > 0.f ? 1.f : 0.f;
+}
+
 // MODE 0: sums of z and z^2                        (forward statistics)
-// MODE 1: sums of g and g * xhat, g = dA * mask * ELU'(z*scale+shift), xhat = (z-mean)*invstd
-template <int MODE>
+// MODE 1: sums of g and g * xhat, g = dA * mask * act'(z*scale+shift), xhat = (z-mean)*invstd
+template <int MODE, int ACT>
 __global__ __launch_bounds__(NT) void k_colsum(const float* __restrict__ Z,
                                                const float* __restrict__ dA,
                                                const float* __restrict__ mask, int64_t M, int N,
@@ -67,7 +81,7 @@ __global__ __launch_bounds__(NT) void k_colsum(const float* __restrict__ Z,
       const f32x4 m = mask ? ld4(mask + r * N + c) : f32x4{1.f, 1.f, 1.f, 1.f};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float g = da[j] * bn_elu_grad(z[j], sc[j], sh[j]) * m[j];
+        const float g = da[j] * bn_act_grad<ACT>(z[j], sc[j], sh[j]) * m[j];
         const float xh = (z[j] - mu[j]) * is[j];
         s0[j] += (double)g;
         s1[j] += (double)g * (double)xh;
@@ -235,7 +249,8 @@ __global__ __launch_bounds__(NT) void k_bn_reduce_tail(
   }
 }
 
-// A = ELU(Z * scale + shift) [* mask]; per-column constants in registers (thread mapping above)
+// A = act(Z * scale + shift) [* mask]; per-column constants in registers (thread mapping above)
+template <int ACT>
 __global__ __launch_bounds__(NT) void k_bn_act(const float* __restrict__ Z, int64_t M, int N,
                                                const float* __restrict__ scale,
                                                const float* __restrict__ shift,
@@ -249,7 +264,7 @@ __global__ __launch_bounds__(NT) void k_bn_act(const float* __restrict__ Z, int6
     const f32x4 z = ld4(Z + r * N + c);
     f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = elu_f(fmaf(z[j], sc[j], sh[j]));
+    for (int j = 0; j < 4; ++j) o[j] = act_f<ACT>(fmaf(z[j], sc[j], sh[j]));
     if (mask) o *= ld4(mask + r * N + c);
     st4(A + r * N + c, o);
   }
@@ -257,7 +272,8 @@ __global__ __launch_bounds__(NT) void k_bn_act(const float* __restrict__ Z, int6
 
 // dZ = scale * (g - sums0/count - xhat * sums1/count)   (training; torch batch_norm backward)
 // dZ = scale * g                                         (eval)
-// g = dA * mask * ELU'(Z*scale+shift), xhat = (Z - mean) * invstd.
+// g = dA * mask * act'(Z*scale+shift), xhat = (Z - mean) * invstd.
+template <int ACT>
 __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const float* __restrict__ dA,
                                                      const float* __restrict__ Z,
                                                      const float* __restrict__ mask, int64_t M,
@@ -287,7 +303,7 @@ __global__ __launch_bounds__(NT) void k_bn_bwd_apply(const float* __restrict__ d
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float g = da[j] * bn_elu_grad(z[j], sc[j], sh[j]) * m[j];
+      const float g = da[j] * bn_act_grad<ACT>(z[j], sc[j], sh[j]) * m[j];
       if (training) {
         const float xh = (z[j] - mu[j]) * is[j];
         o[j] = sc[j] * (g - mg[j] - xh * mgx[j]);
@@ -328,8 +344,8 @@ extern "C" int lgnn_bn_stats(const float* Z, int64_t M, int N, double* sums, voi
   hipStream_t s = as_stream(stream);
   const int P = row_blocks(M);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(k_colsum<0>, dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z, nullptr, nullptr,
-                     M, N, nullptr, nullptr, nullptr, nullptr, part);
+  hipLaunchKernelGGL((k_colsum<0, LGNN_ACT_ELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
+                     nullptr, nullptr, M, N, nullptr, nullptr, nullptr, nullptr, part);
   LGNN_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)),
                      dim3(NT), 0, s, part, P, 2 * N, sums);
@@ -353,13 +369,49 @@ extern "C" int lgnn_bn_finalize(const double* sums, double count, const float* g
   return LGNN_OK;
 }
 
-extern "C" int lgnn_bn_act(const float* Z, int64_t M, int N, const float* scale,
-                           const float* shift, const float* mask, float* A, void* stream) {
+extern "C" int lgnn_bn_act_a(const float* Z, int64_t M, int N, const float* scale,
+                             const float* shift, const float* mask, int act, float* A,
+                             void* stream) {
   if (M < 0 || N <= 0 || (N & 3) || !scale || !shift || (M > 0 && (!Z || !A)))
     return LGNN_EINVAL;
+  if (act != LGNN_ACT_ELU && act != LGNN_ACT_RELU) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_bn_act, ew_grid(M, N), dim3(NT), 0, as_stream(stream), Z, M, N, scale,
-                     shift, mask, A);
+  if (act == LGNN_ACT_ELU)
+    hipLaunchKernelGGL(k_bn_act<LGNN_ACT_ELU>, ew_grid(M, N), dim3(NT), 0, as_stream(stream), Z,
+                       M, N, scale, shift, mask, A);
+  else
+    hipLaunchKernelGGL(k_bn_act<LGNN_ACT_RELU>, ew_grid(M, N), dim3(NT), 0, as_stream(stream), Z,
+                       M, N, scale, shift, mask, A);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" int lgnn_bn_act(const float* Z, int64_t M, int N, const float* scale,
+                           const float* shift, const float* mask, float* A, void* stream) {
+  return lgnn_bn_act_a(Z, M, N, scale, shift, mask, LGNN_ACT_ELU, A, stream);
+}
+
+extern "C" int lgnn_bn_bwd_stats_a(const float* dA, const float* Z, const float* mask,
+                                   int64_t M, int N, const float* scale, const float* shift,
+                                   const float* mean, const float* invstd, int act, double* sums,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (act != LGNN_ACT_ELU && act != LGNN_ACT_RELU) return LGNN_EINVAL;
+  if (M < 0 || N <= 0 || (N & 3) || !sums || !scale || !shift || !mean || !invstd)
+    return LGNN_EINVAL;
+  if (M > 0 && (!dA || !Z)) return LGNN_EINVAL;
+  if (!workspace || workspace_bytes < lgnn_bn_workspace_bytes(M, N)) return LGNN_ENOSPC;
+  hipStream_t s = as_stream(stream);
+  const int P = row_blocks(M);
+  double* part = static_cast<double*>(workspace);
+  if (act == LGNN_ACT_ELU)
+    hipLaunchKernelGGL((k_colsum<1, LGNN_ACT_ELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
+                       dA, mask, M, N, scale, shift, mean, invstd, part);
+  else
+    hipLaunchKernelGGL((k_colsum<1, LGNN_ACT_RELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
+                       dA, mask, M, N, scale, shift, mean, invstd, part);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)),
+                     dim3(NT), 0, s, part, P, 2 * N, sums);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }
@@ -368,20 +420,8 @@ extern "C" int lgnn_bn_bwd_stats(const float* dA, const float* Z, const float* m
                                  int N, const float* scale, const float* shift, const float* mean,
                                  const float* invstd, double* sums, void* workspace,
                                  size_t workspace_bytes, void* stream) {
-  if (M < 0 || N <= 0 || (N & 3) || !sums || !scale || !shift || !mean || !invstd)
-    return LGNN_EINVAL;
-  if (M > 0 && (!dA || !Z)) return LGNN_EINVAL;
-  if (!workspace || workspace_bytes < lgnn_bn_workspace_bytes(M, N)) return LGNN_ENOSPC;
-  hipStream_t s = as_stream(stream);
-  const int P = row_blocks(M);
-  double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(k_colsum<1>, dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z, dA, mask, M, N,
-                     scale, shift, mean, invstd, part);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)),
-                     dim3(NT), 0, s, part, P, 2 * N, sums);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return lgnn_bn_bwd_stats_a(dA, Z, mask, M, N, scale, shift, mean, invstd, LGNN_ACT_ELU, sums,
+                             workspace, workspace_bytes, stream);
 }
 
 extern "C" int lgnn_bn_partials_reduce(const double* part, int num_partials, int N,
@@ -418,19 +458,24 @@ extern "C" int lgnn_bn_partials_finalize(const double* part, int num_partials, i
   return LGNN_OK;
 }
 
-extern "C" int lgnn_bn_bwd_apply(const float* dA, const float* Z, const float* mask, int64_t M,
-                                 int N, const float* scale, const float* shift, const float* mean,
-                                 const float* invstd, const double* sums, double count,
-                                 int training, float* dZ, float* dgamma, float* dbeta,
-                                 void* stream) {
+extern "C" int lgnn_bn_bwd_apply_a(const float* dA, const float* Z, const float* mask,
+                                   int64_t M, int N, const float* scale, const float* shift,
+                                   const float* mean, const float* invstd, int act,
+                                   const double* sums, double count, int training, float* dZ,
+                                   float* dgamma, float* dbeta, void* stream) {
+  if (act != LGNN_ACT_ELU && act != LGNN_ACT_RELU) return LGNN_EINVAL;
   if (M < 0 || N <= 0 || (N & 3) || !scale || !shift || !mean || !invstd || !sums)
     return LGNN_EINVAL;
   if (training && count <= 0.0) return LGNN_EINVAL;
   hipStream_t s = as_stream(stream);
   if (M > 0) {
     if (!dA || !Z || !dZ) return LGNN_EINVAL;
-    hipLaunchKernelGGL(k_bn_bwd_apply, ew_grid(M, N), dim3(NT), 0, s, dA, Z, mask, M, N, scale,
-                       shift, mean, invstd, sums, count, training, dZ);
+    if (act == LGNN_ACT_ELU)
+      hipLaunchKernelGGL(k_bn_bwd_apply<LGNN_ACT_ELU>, ew_grid(M, N), dim3(NT), 0, s, dA, Z, mask,
+                         M, N, scale, shift, mean, invstd, sums, count, training, dZ);
+    else
+      hipLaunchKernelGGL(k_bn_bwd_apply<LGNN_ACT_RELU>, ew_grid(M, N), dim3(NT), 0, s, dA, Z,
+                         mask, M, N, scale, shift, mean, invstd, sums, count, training, dZ);
     LGNN_LAUNCH_CHECK();
   }
   if (dgamma || dbeta) {
@@ -439,4 +484,13 @@ extern "C" int lgnn_bn_bwd_apply(const float* dA, const float* Z, const float* m
     LGNN_LAUNCH_CHECK();
   }
   return LGNN_OK;
+}
+
+extern "C" int lgnn_bn_bwd_apply(const float* dA, const float* Z, const float* mask, int64_t M,
+                                 int N, const float* scale, const float* shift, const float* mean,
+                                 const float* invstd, const double* sums, double count,
+                                 int training, float* dZ, float* dgamma, float* dbeta,
+                                 void* stream) {
+  return lgnn_bn_bwd_apply_a(dA, Z, mask, M, N, scale, shift, mean, invstd, LGNN_ACT_ELU, sums,
+                             count, training, dZ, dgamma, dbeta, stream);
 }

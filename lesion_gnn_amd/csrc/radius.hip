@@ -24,23 +24,13 @@
 // int64 sorted. One thread per query; a block's queries are consecutive nodes, so the candidates
 // of its graphs are one contiguous node range, staged through LDS in chunks (as k_knn).
 #include "common.h"
+#include "geom.h"
 
 namespace {
 
 constexpr int QT = 256;      // queries (threads) per block
 constexpr int CHUNK = 1024;  // candidates staged per round
 constexpr int ST = 1024;     // scan threads
-
-__device__ __forceinline__ double sqd(const double* a, const double* b, int D) {
-#pragma clang fp contract(off)
-  const double dx = a[0] - b[0], dy = a[1] - b[1];
-  double s = dx * dx + dy * dy;
-  if (D == 3) {
-    const double dz = a[2] - b[2];
-    s = s + dz * dz;
-  }
-  return s;
-}
 
 // WRITE = false: cnt[q] = the query's edge count; WRITE = true: its edges at off[q]
 template <int D, bool WRITE>
@@ -200,5 +190,210 @@ extern "C" int lgnn_radius_graph(const double* pos, int64_t N, int dims, const i
     hipLaunchKernelGGL((k_radius<3, true>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
                        loop, nullptr, w.off, num_edges, edge_index);
   LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Bipartite form: torch_cluster.radius(x, y, r, batch_x, batch_y, max_num_neighbors) — the queries
+// y (PointNet++: the FPS centroids, in selection order) and the candidates x are different point
+// sets over the same graphs. Same walk, same arithmetic, same two passes as above; no self pair
+// to drop. The queries of a block are consecutive query rows, hence of consecutive graphs, so
+// their candidates are the contiguous range ptr_x[first graph] .. ptr_x[last graph + 1], staged
+// through LDS in chunks. A query's graph is found in ptr_y (queries carry no batch vector).
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// the graph g with ptr[g] <= i < ptr[g + 1] (the last g with ptr[g] <= i: empty graphs skipped)
+__device__ __forceinline__ int graph_of(const int32_t* __restrict__ ptr, int B, int64_t i) {
+  int lo = 0, hi = B - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (ptr[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+template <int D, bool WRITE>
+__global__ __launch_bounds__(QT) void k_radius_pairs(const double* __restrict__ x,
+                                                     const double* __restrict__ y, int64_t Ny,
+                                                     const int32_t* __restrict__ ptrx,
+                                                     const int32_t* __restrict__ ptry, int B,
+                                                     double r2, int limit,
+                                                     int32_t* __restrict__ cnt,
+                                                     const int64_t* __restrict__ off, int64_t E,
+                                                     int64_t* __restrict__ pairs) {
+  __shared__ double cp[CHUNK * D];
+  const int64_t q0 = (int64_t)blockIdx.x * QT;
+  const int64_t q = q0 + threadIdx.x;
+  const int64_t qlast = q0 + QT - 1 < Ny - 1 ? q0 + QT - 1 : Ny - 1;
+  const int64_t cbeg = ptrx[graph_of(ptry, B, q0)], cend = ptrx[graph_of(ptry, B, qlast) + 1];
+  const bool active = q < Ny;
+  int64_t gs = 0, ge = 0;
+  double pq[D];
+  if (active) {
+    const int g = graph_of(ptry, B, q);
+    gs = ptrx[g];
+    ge = ptrx[g + 1];
+#pragma unroll
+    for (int d = 0; d < D; ++d) pq[d] = y[q * D + d];
+  }
+  int taken = 0;
+  const int64_t base = WRITE && active ? off[q] : 0;
+  for (int64_t c0 = cbeg; c0 < cend; c0 += CHUNK) {
+    const int64_t c1 = c0 + CHUNK < cend ? c0 + CHUNK : cend;
+    if (!__syncthreads_or(active && taken < limit && ge > c0)) break;
+    for (int64_t i = c0 * D + threadIdx.x; i < c1 * D; i += QT) cp[i - c0 * D] = x[i];
+    __syncthreads();
+    if (!active || taken >= limit) continue;
+    const int64_t lo = gs > c0 ? gs : c0, hi = ge < c1 ? ge : c1;
+    for (int64_t c = lo; c < hi && taken < limit; ++c) {
+      if (sqd(pq, cp + (c - c0) * D, D) < r2) {
+        if constexpr (WRITE) {
+          if (base + taken < E) {  // E = offsets[Ny]: a short buffer is not overrun
+            pairs[base + taken] = q;
+            pairs[E + base + taken] = c;
+          }
+        }
+        ++taken;
+      }
+    }
+  }
+  if constexpr (!WRITE) {
+    if (active) cnt[q] = taken;
+  }
+}
+
+int pairs_args_ok(const double* x, int64_t Nx, const double* y, int64_t Ny, int dims,
+                  const int32_t* ptrx, const int32_t* ptry, int64_t B, double r,
+                  int max_num_neighbors) {
+  if (Nx < 0 || Ny < 0 || B < 0 || (dims != 2 && dims != 3) || !(r >= 0.0) ||
+      max_num_neighbors < 1)
+    return 0;
+  if (Nx > INT32_MAX || Ny > INT32_MAX || B > INT32_MAX) return 0;
+  if ((Nx > 0 && !x) || (Ny > 0 && !y)) return 0;
+  if (Ny > 0 && (B == 0 || !ptrx || !ptry)) return 0;
+  return 1;
+}
+
+// Transpose of a pair list grouped by query with ascending candidates: per candidate j the pairs
+// naming it, in ascending pair order. One thread per candidate: it walks the query rows of its
+// graph and looks j up in each row's ascending candidate list (binary search; a row holds at most
+// max_num_neighbors). PLACE = false: cnt[j]; true: perm[tptr[j] + rank] = pair index. No atomics.
+template <bool PLACE>
+__global__ __launch_bounds__(QT) void k_pairs_transpose(const int64_t* __restrict__ col,
+                                                        const int64_t* __restrict__ rowoff,
+                                                        const int32_t* __restrict__ ptrx,
+                                                        const int32_t* __restrict__ ptry, int B,
+                                                        int64_t Nx, int32_t* __restrict__ cnt,
+                                                        const int64_t* __restrict__ tptr,
+                                                        int64_t* __restrict__ perm) {
+  const int64_t j = (int64_t)blockIdx.x * QT + threadIdx.x;
+  if (j >= Nx) return;
+  const int g = graph_of(ptrx, B, j);
+  int64_t w = PLACE ? tptr[j] : 0;
+  int n = 0;
+  for (int64_t i = ptry[g]; i < ptry[g + 1]; ++i) {
+    int64_t lo = rowoff[i], hi = rowoff[i + 1];
+    while (lo < hi) {  // the first pair of row i with col >= j
+      const int64_t mid = (lo + hi) >> 1;
+      if (col[mid] < j) lo = mid + 1; else hi = mid;
+    }
+    if (lo < rowoff[i + 1] && col[lo] == j) {
+      if constexpr (PLACE) perm[w++] = lo;
+      ++n;
+    }
+  }
+  if constexpr (!PLACE) cnt[j] = n;
+}
+
+}  // namespace
+
+extern "C" size_t lgnn_radius_pairs_workspace_bytes(int64_t num_queries) {
+  return lgnn_radius_workspace_bytes(num_queries);
+}
+
+extern "C" int lgnn_radius_pairs_count(const double* x, int64_t Nx, const double* y, int64_t Ny,
+                                       int dims, const int32_t* ptr_x, const int32_t* ptr_y,
+                                       int64_t B, double r, int max_num_neighbors,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (!pairs_args_ok(x, Nx, y, Ny, dims, ptr_x, ptr_y, B, r, max_num_neighbors))
+    return LGNN_EINVAL;
+  if (!workspace || workspace_bytes < lgnn_radius_workspace_bytes(Ny)) return LGNN_ENOSPC;
+  hipStream_t s = as_stream(stream);
+  const RadiusWs w = radius_ws(workspace, Ny);
+  if (Ny == 0) {
+    if (hipMemsetAsync(w.off, 0, sizeof(int64_t), s) != hipSuccess) return (int)hipGetLastError();
+    return LGNN_OK;
+  }
+  const double r2 = r * r;
+  const dim3 grid((unsigned)((Ny + QT - 1) / QT));
+  if (dims == 2)
+    hipLaunchKernelGGL((k_radius_pairs<2, false>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
+                       (int)B, r2, max_num_neighbors, w.cnt, nullptr, 0, nullptr);
+  else
+    hipLaunchKernelGGL((k_radius_pairs<3, false>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
+                       (int)B, r2, max_num_neighbors, w.cnt, nullptr, 0, nullptr);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(ST), 0, s, w.cnt, Ny, w.off);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" int lgnn_radius_pairs(const double* x, int64_t Nx, const double* y, int64_t Ny,
+                                 int dims, const int32_t* ptr_x, const int32_t* ptr_y, int64_t B,
+                                 double r, int max_num_neighbors, int64_t* pairs,
+                                 int64_t num_pairs, const void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (!pairs_args_ok(x, Nx, y, Ny, dims, ptr_x, ptr_y, B, r, max_num_neighbors))
+    return LGNN_EINVAL;
+  if (num_pairs < 0 || (num_pairs > 0 && !pairs)) return LGNN_EINVAL;
+  if (!workspace || workspace_bytes < lgnn_radius_workspace_bytes(Ny)) return LGNN_ENOSPC;
+  if (Ny == 0 || num_pairs == 0) return LGNN_OK;
+  const RadiusWs w = radius_ws(const_cast<void*>(workspace), Ny);
+  const double r2 = r * r;
+  const dim3 grid((unsigned)((Ny + QT - 1) / QT));
+  hipStream_t s = as_stream(stream);
+  if (dims == 2)
+    hipLaunchKernelGGL((k_radius_pairs<2, true>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
+                       (int)B, r2, max_num_neighbors, nullptr, w.off, num_pairs, pairs);
+  else
+    hipLaunchKernelGGL((k_radius_pairs<3, true>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
+                       (int)B, r2, max_num_neighbors, nullptr, w.off, num_pairs, pairs);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" size_t lgnn_pairs_transpose_workspace_bytes(int64_t num_candidates) {
+  return num_candidates > 0 ? (size_t)num_candidates * sizeof(int32_t) : 0;
+}
+
+extern "C" int lgnn_pairs_transpose(const int64_t* col, const int64_t* rowoff, int64_t Ny,
+                                    int64_t num_pairs, const int32_t* ptr_x,
+                                    const int32_t* ptr_y, int64_t B, int64_t Nx, int64_t* tptr,
+                                    int64_t* perm, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  if (Nx < 0 || Ny < 0 || B < 0 || num_pairs < 0 || !tptr || Nx > INT32_MAX || B > INT32_MAX)
+    return LGNN_EINVAL;
+  if (Nx > 0 && (B == 0 || !ptr_x || !ptr_y || !rowoff)) return LGNN_EINVAL;
+  if (num_pairs > 0 && (!col || !perm || Nx == 0)) return LGNN_EINVAL;
+  if (Nx > 0 && (!workspace || workspace_bytes < lgnn_pairs_transpose_workspace_bytes(Nx)))
+    return LGNN_ENOSPC;
+  hipStream_t s = as_stream(stream);
+  if (Nx == 0) {
+    if (hipMemsetAsync(tptr, 0, sizeof(int64_t), s) != hipSuccess) return (int)hipGetLastError();
+    return LGNN_OK;
+  }
+  int32_t* cnt = static_cast<int32_t*>(workspace);
+  const dim3 grid((unsigned)((Nx + QT - 1) / QT));
+  hipLaunchKernelGGL(k_pairs_transpose<false>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,
+                     (int)B, Nx, cnt, nullptr, nullptr);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(ST), 0, s, cnt, Nx, tptr);
+  LGNN_LAUNCH_CHECK();
+  if (num_pairs > 0) {
+    hipLaunchKernelGGL(k_pairs_transpose<true>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,
+                       (int)B, Nx, nullptr, tptr, perm);
+    LGNN_LAUNCH_CHECK();
+  }
   return LGNN_OK;
 }

@@ -10,6 +10,9 @@
 - `set_attention`   segmented multi-head attention over ragged sets; `mab` / `isab`: PyG's
                     MultiheadAttentionBlock / InducedSetAttentionBlock as ONE autograd node each;
                     `res_norm` (residual + activation + LayerNorm), `set_readout`
+- `edge_sub`        PointNetConv's split first Linear over the pairs of a cluster.PairGraph;
+                    `bn_act_rows` (BatchNorm + ReLU / ELU [+ dropout mask] over rows),
+                    `segment_max` (the max aggregation and global_max_pool)
 """
 from __future__ import annotations
 
@@ -2626,3 +2629,141 @@ def isab(x, ind, params1: list, params2: list, ptr, rows: int, num_sets: int, he
                                    (list(params1[6:]) + list(params2[6:])) if ln else [], ptr,
                                    int(rows), num_sets, int(heads), mask1, mask2)[0]
     return _Isab.apply(x, ind, ptr, rows, num_sets, heads, mask1, mask2, *params1, *params2)
+
+
+# ----------------------------------------------------------------------------------------------
+# PointNet++ (cluster.py builds the PairGraph): the split first Linear of PointNetConv's per-edge
+# MLP, BatchNorm + activation over rows, the max aggregation. Eager only (data-dependent shapes).
+# ----------------------------------------------------------------------------------------------
+
+
+def segment_sum(X, ptr, perm, S: int, sign: float) -> torch.Tensor:
+    """out [S, C] = sign * the sum of X's rows perm[ptr[s] .. ptr[s+1]) (perm None: the rows
+    themselves), ascending."""
+    out = torch.empty(S, X.size(1), dtype=torch.float32, device=X.device)
+    _lib.call("lgnn_segment_sum", X, ptr, perm, S, X.size(1), float(sign), out, _s(X.device))
+    return out
+
+
+class _EdgeSub(torch.autograd.Function):
+    """(Z, sums) = (U[col] - V[row], Z's fp64 column sums (sum z, sum z^2)); backward: dU and dV
+    as segment sums of dZ (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, U, V, pg):
+        _lib.require_gpu(U, V)
+        U, V = _f32c(U), _f32c(V)
+        E, C = pg.num_pairs, U.size(1)
+        if U.size(0) != pg.num_candidates or V.size(0) != pg.num_queries or V.size(1) != C:
+            raise ValueError("edge_sub: U [candidates, C] and V [queries, C] expected")
+        Z = torch.empty(E, C, dtype=torch.float32, device=U.device)
+        sums = torch.empty(2 * C, dtype=torch.float64, device=U.device)
+        ws = _bn_ws(E, C, U.device)
+        _lib.call("lgnn_edge_sub_fwd", U, V, pg.row, pg.col, E, C, Z, sums, ws, ws.numel(),
+                  _s(U.device))
+        ctx.pg = pg
+        ctx.mark_non_differentiable(sums)
+        return Z, sums
+
+    @staticmethod
+    def backward(ctx, dZ, _):
+        pg = ctx.pg
+        dZ = _f32c(dZ)
+        dU = dV = None
+        if ctx.needs_input_grad[0]:
+            tptr, perm = pg.transpose()
+            dU = segment_sum(dZ, tptr, perm, pg.num_candidates, 1.0)
+        if ctx.needs_input_grad[1]:
+            dV = segment_sum(dZ, pg.rowoff, None, pg.num_queries, -1.0)
+        return dU, dV, None
+
+
+def edge_sub(U, V, pg):
+    return _EdgeSub.apply(U, V, pg)
+
+
+class _BnAct(torch.autograd.Function):
+    """A = act(BatchNorm(Z)) [* mask] over rows (torch.nn.BatchNorm1d semantics; bn None: no
+    norm, A = act(Z) [* mask]). sums: Z's column sums when its producer formed them."""
+
+    @staticmethod
+    def forward(ctx, Z, gamma, beta, bn, training, act, mask, sums):
+        _lib.require_gpu(Z)
+        Z = _f32c(Z)
+        M, N = Z.shape
+        dev = Z.device
+        if bn is None:
+            scale = torch.ones(N, dtype=torch.float32, device=dev)
+            shift = torch.zeros(N, dtype=torch.float32, device=dev)
+            mean = invstd = scale
+            training = False
+        else:
+            if training and M == 0:
+                raise ValueError("BatchNorm in training mode needs at least one row")
+            if training and sums is None:
+                sums = bn_stats(Z)
+            mean, invstd, scale, shift = bn_finalize(sums, float(M), bn, training, N, dev)
+        A = torch.empty_like(Z)
+        _lib.call("lgnn_bn_act_a", Z, M, N, scale, shift, mask, int(act), A, _s(dev))
+        ctx.save_for_backward(Z, scale, shift, mean, invstd, mask)
+        ctx.meta = (bn is not None, bool(training), int(act))
+        return A
+
+    @staticmethod
+    def backward(ctx, dA):
+        Z, scale, shift, mean, invstd, mask = ctx.saved_tensors
+        has_bn, training, act = ctx.meta
+        dA = _f32c(dA)
+        M, N = Z.shape
+        dev = Z.device
+        dg = db = None
+        if has_bn:
+            sums = torch.empty(2 * N, dtype=torch.float64, device=dev)
+            ws = _bn_ws(M, N, dev)
+            _lib.call("lgnn_bn_bwd_stats_a", dA, Z, mask, M, N, scale, shift, mean, invstd, act,
+                      sums, ws, ws.numel(), _s(dev))
+            if ctx.needs_input_grad[1]:
+                dg = torch.empty(N, dtype=torch.float32, device=dev)
+                db = torch.empty(N, dtype=torch.float32, device=dev)
+        else:
+            sums = torch.zeros(2 * N, dtype=torch.float64, device=dev)  # not read (eval form)
+        dZ = torch.empty_like(Z)
+        _lib.call("lgnn_bn_bwd_apply_a", dA, Z, mask, M, N, scale, shift, mean, invstd, act, sums,
+                  float(max(M, 1)), int(training), dZ, dg, db, _s(dev))
+        return dZ, dg, db, None, None, None, None, None
+
+
+def bn_act_rows(Z, bn, training: bool, act: int, mask=None, sums=None):
+    """act(bn(Z)) [* mask]; bn a torch.nn.BatchNorm1d (affine) or None."""
+    gamma, beta = (bn.weight, bn.bias) if bn is not None else (None, None)
+    return _BnAct.apply(Z, gamma, beta, bn, training, act, mask, sums)
+
+
+class _SegmentMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, ptr, S):
+        _lib.require_gpu(X, ptr)
+        X = _f32c(X)
+        C = X.size(1)
+        out = torch.empty(S, C, dtype=torch.float32, device=X.device)
+        arg = torch.empty(S, C, dtype=torch.int32, device=X.device)
+        _lib.call("lgnn_segment_max_fwd", X, ptr, S, C, out, arg, _s(X.device))
+        ctx.save_for_backward(arg, ptr)
+        ctx.rows = X.size(0)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        arg, ptr = ctx.saved_tensors
+        S, C = arg.shape
+        dX = torch.empty(ctx.rows, C, dtype=torch.float32, device=dout.device)
+        _lib.call("lgnn_segment_max_bwd", _f32c(dout), arg, ptr, S, C, dX, _s(dout.device))
+        return dX, None, None
+
+
+def segment_max(X, ptr, num_segments: int):
+    """out [S, C] = the max over each segment's rows (ptr int64 [S + 1], the segments tiling X's
+    rows in order); 0 for an empty segment. The gradient goes to the lowest row that gave it."""
+    if ptr.dtype != torch.int64 or ptr.numel() != num_segments + 1:
+        raise ValueError("segment_max: ptr must be int64 [num_segments + 1]")
+    return _SegmentMax.apply(X, ptr, int(num_segments))
