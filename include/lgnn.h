@@ -622,7 +622,9 @@ int lgnn_adam_step(int n, float* const* params, const float* const* grads, float
  * pass, one launch. Replaces the same autograd chain as lgnn_gcn_stack_bwd (reference path:
  * global_mean/add_pool backward, per conv G = Â^T dZ, dW += G^T H, dH = G W, ELU', and in_proj
  * dW) for tiles with tile_open[t] == 0, L = 1 or 2 convs (3 through the _all / _ce entries
- * below), every width <= 128 and % 4 == 0.
+ * below), every width <= 128 and % 4 == 0. L <= 2: in_proj (no activation) is folded behind the
+ * first conv — no dH_0 = G_1 W_1 per tile; the workgroup sums T = G_1^T X and g = colsum G_1 over
+ * its tiles and writes dW_0 = W_1^T T, db_0 = W_1^T g (the same sums in another order).
  *   planes_t: the transposed weight planes of lgnn_weight_planes (all L + 1 layers);
  *   H[0..L]: layer outputs (H[0] = in_proj output); X: model input; widths[0..L+1];
  *   dWp / dbp: per-layer partial slabs with num_partials = lgnn_gcn_stack_bwd_partials(M)

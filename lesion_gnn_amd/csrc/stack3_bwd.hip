@@ -480,7 +480,12 @@ namespace lgnn_s3 {
 //   * G^T has its own LDS image, so the H image of the dW product and the G^T image of the dH
 //     product coexist (two barriers per conv layer);
 //   * the next tile's CSR block is prefetched during the current tile (idx head/body), and the
-//     next layer's H_{l-1} rows are issued before the current layer's G products.
+//     next layer's H_{l-1} rows are issued before the current layer's G products;
+//   * in_proj is folded behind the first conv (L <= 2): it has no activation, so dH_0 = G_1 W_1
+//     feeds dW_0 = dH_0^T X linearly and dW_0 = W_1^T (G_1^T X). Per tile the first conv takes
+//     no dH: its product pass adds T += G_1^T X (the X image in the G image's place, dW_0's
+//     accumulators) beside dW_1 += G_1^T H_0, and g += colsum G_1. After its last tile the
+//     workgroup forms dW_0 = W_1^T T and db_0 = W_1^T g once, before the slot write.
 // Per tile HBM traffic: H_L, H_{L-1}, ..., H_0, X read once (the algorithmic bytes).
 // ==============================================================================================
 
@@ -546,7 +551,8 @@ __device__ __forceinline__ float head_dl(const FBwdArgs& a, float raw, float wt,
 
 struct FBwdSmem {
   unsigned char Img[3][TM * AROW];  // 48 KiB: H_{l-1} (or X) feature-major [k][perm16 m]
-  unsigned char Gt[3][TM * AROW];   // 48 KiB: G node-major [m][perm16 n]
+  unsigned char Gt[3][TM * AROW];   // 48 KiB: G node-major [m][perm16 n]; at the folded first
+                                    // conv X feature-major instead (as Img)
   unsigned char Adj[3][ADJ_PLANE];  // 27 KiB: Â^T planes; first 16 KiB fp32 while summed
   float pscale[TM];
   int pg[TM];
@@ -659,9 +665,10 @@ __device__ __forceinline__ void adj_write(FBwdSmem& sm, const AdjPlanes& o) {
   }
 }
 
-// AG: the next tile's Â^T planes are split during this tile's in_proj phase (VALU and LDS work
-// beside the dW_0 MFMAs) instead of in the next tile's prologue; -DLGNN_S3F_NOPIPE: in the
-// prologue (the round-3 order; A/B builds only)
+// AG: the next tile's Â^T planes are split during this tile's last product pass (the first
+// conv's dW_1 / T products, or XIN's dZ_0 store: VALU and LDS work beside the MFMAs) instead of
+// in the next tile's prologue; -DLGNN_S3F_NOPIPE: in the prologue (the round-3 order; A/B builds
+// only)
 #ifdef LGNN_S3F_NOPIPE
 constexpr bool kAdjPipe = false;
 #else
@@ -786,7 +793,8 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       idx_load_body(R, col, w);
     }
   }
-  if constexpr (AG && kAdjPipe) {  // the first tile's Â^T planes (later tiles': in_proj phase)
+  // the first tile's Â^T planes (later tiles': during the previous tile's last product pass)
+  if constexpr (AG && kAdjPipe) {
     if (t < ntiles) {
       if (fresh_tid() == 0) sm.flag = 0;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -942,11 +950,13 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
     const bool aexact = __builtin_amdgcn_readfirstlane(sm.flag) == 0;
     STAMP(stamp++);
 
-    f32x16 xp[2];  // X rows of the in_proj phase (issued during the last conv's dH)
+    f32x16 xp[2];  // X rows of the first conv's T product (issued during the last conv's dW)
 #pragma unroll
     for (int l = L; l >= 1; --l) {
       const int K = a.width[l];
       const bool elu_prev = l >= 2;
+      // the first conv with in_proj folded behind it: no dH, T += G_1^T X beside dW_1
+      const bool fold = !XIN && l == 1;
       // H_{l-1} rows (P layout, feature k on the lane): issued first, consumed by the image
       // write after the G products and by ELU' at the end of the layer
       f32x16 hp[2];
@@ -967,6 +977,11 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       }
       u32x4 dzp[4][3];
       split_p(dz, dzp);
+      if (fold && L == 1) {  // one conv: no earlier layer to issue the X rows in (dZ is split)
+        const int tq = fresh_tid();
+        const int h = (tq >> 5) & 1, k = 32 * (tq >> 6) + (tq & 31);
+        load_pt(xp, a.X, (ABL & 16) ? 0 : M, r0, a.width[0], k, a.width[0], h);
+      }
       // G = Â^T dZ (P layout)
       f32x16 g[2] = {f32x16{}, f32x16{}};
       {
@@ -1000,10 +1015,34 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       // G's operand planes, split once: dW's A operand below, and (transposed) the G image
       u32x4 gp[4][3];
       split_p(g, gp);
+      if (fold) {
+        // g += colsum G_1 (db_0 = W_1^T g at the end), as db_l above; and X -> feature-major
+        // image in the G image's place (no dH below the first conv: its G image is not built)
+        const int tq = fresh_tid();
+        const int h = (tq >> 5) & 1, li = tq & 31, k = 32 * (tq >> 6) + li;
+        float sacc = 0.f;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) sacc += g[q][r];
+        sacc += __shfl_xor(sacc, 32, 64);
+        dbacc[0] += sacc;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int gq = 0; gq < 4; ++gq) {
+            u32x2 o[3];
+            split4(f32x4{xp[q][4 * gq], xp[q][4 * gq + 1], xp[q][4 * gq + 2], xp[q][4 * gq + 3]},
+                   o);
+            const int off = hf_off(k, 32 * q + 8 * gq + 4 * h);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) sts8(sm.Gt[p] + off, o[p]);
+          }
+      }
       // G -> node-major image [m][perm16 n] for dH = G W_l: each quad of lanes (4 features,
       // 4 nodes per packed pair of planes) transposes its 4 x 4 blocks of bf16 by DPP + v_perm,
       // so a lane holds four consecutive features of one node (no G^T = dZ^T Â products)
-      {
+      if (!fold) {
         const int tq = fresh_tid();
         const int h = (tq >> 5) & 1, li = tq & 31, wv = tq >> 6, qi = li & 3;
 #pragma unroll
@@ -1054,7 +1093,7 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
                                                                      512 * (2 * pair + s2));
       };
       u32x4 wa[3][2], wb[3][2];
-      load_w2(wa, 0);
+      if (!fold) load_w2(wa, 0);
       lds_barrier();  // both images complete
       // the last conv's Â^T reads are done: the next tile's planes load into LDS behind the
       // remaining phases of this tile
@@ -1063,19 +1102,75 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       }
       // ... and the next tile's H_L rows (the prologue's reads of sm.hl passed many barriers)
       if (l == 1 && has_next) hl_issue(sm, a.H[L], M, tn, NLast);
-      if (l == 1) {  // the next tile's graph ids (their sizes follow in the in_proj phase)
+      if (l == 1) {  // the next tile's graph ids (their sizes follow midway through the products)
         const int tq = fresh_tid();
         const int64_t row = tn * TM + tq;
         pre_g = (has_next && tq < TM && row < M) ? a.batch[row] : 0;
+        // (pipelined Â) cleared for the next tile's split; this tile's value is in aexact
+        if constexpr (AG && kAdjPipe && !XIN) {
+          if (tq == 0) sm.flag = 0;
+        }
       }
-      // this tile's X rows for the in_proj phase, in flight from the first conv's dW on (issued
-      // at the last conv they crowded that phase's load queue: in-step 107.6 -> 106.0 us)
-      if (!XIN && l == L) {
+      // this tile's X rows for the first conv's T product, in flight from the last conv's dW on
+      if (!XIN && l == L && L > 1) {
         const int tq = fresh_tid();
         const int h = (tq >> 5) & 1, k = 32 * (tq >> 6) + (tq & 31);
         load_pt(xp, a.X, (ABL & 16) ? 0 : M, r0, a.width[0], k, a.width[0], h);
       }
       STAMP(stamp++);
+      if (fold) {
+        // dW_1 += G_1^T H_0 and T += G_1^T X in one pass over the node steps (A = G_1's planes,
+        // B = the H_0 image and the X image): by associativity dW_0 = dH_0^T X = W_1^T (G_1^T X),
+        // so the product with W_1 runs once per workgroup (below the tile loop) instead of
+        // dH_0 = G_1 W_1 once per tile. Each accumulator takes s = 0..3 in order. Midway the next
+        // tile's prefetches (issued after the barrier above) have landed: its Â is split beside
+        // the second half of the products, and the loads that depend on its graph ids go out.
+        AdjPlanes nap;  // the next tile's Â^T planes (pipe)
+        {
+          const int tq = fresh_tid();
+          const int h = (tq >> 5) & 1, li = tq & 31;
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            if (s == 2) {
+              // (pipelined Â: unconditional — a branch around these barriers and stores made
+              // the register allocator spill; past the last tile the planes written are unused)
+              if constexpr (AG && kAdjPipe) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                lds_barrier();  // every wave's next-tile Â landed (and the cleared flag)
+                nap = adj_split(sm);
+              }
+              const int t2 = fresh_tid();
+              pre_cnt = (has_next && t2 < TM) ? a.gptr[pre_g + 1] - a.gptr[pre_g] : 0;
+              if (has_head(a)) {
+#pragma unroll
+                for (int c = 0; c < kMaxHeadC; ++c)
+                  pre_dl[c] = (has_next && t2 < TM && c < a.C) ? head_raw(a, pre_g, c) : 0.f;
+                if (a.ce.pm) pre_wt = (has_next && t2 < TM) ? a.ce.wt[pre_g] : 0.f;
+              }
+            }
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+              u32x4 hb[3], xb[3];
+              const int off = hf_chunk(32 * kb + li, 2 * s + h);
+#pragma unroll
+              for (int p = 0; p < 3; ++p) hb[p] = lds16(sm.Img[p] + off);
+#pragma unroll
+              for (int p = 0; p < 3; ++p) xb[p] = lds16(sm.Gt[p] + off);
+              if constexpr (!(ABL & 1)) {
+                dw[1][kb] = mfma_s3(gp[s], hb, dw[1][kb]);
+                dw[0][kb] = mfma_s3(gp[s], xb, dw[0][kb]);
+              }
+            }
+            S3F_SB();
+          }
+        }
+        lds_barrier();  // both images read (and the Â scratch); the next tile may overwrite LDS
+        if constexpr (AG && kAdjPipe) {
+          adj_write(sm, nap);
+          lds_barrier();  // the next tile's Â^T planes are in place
+        }
+        STAMP(stamp++);
+      } else {
       // dW_l += G^T H: A = G (P layout, node steps: the planes split above), B = H image rows
       // k = 32 kb + li. Node steps outer: consecutive products go to different accumulators,
       // each accumulator still takes s = 0..3 in order, and gp[s] is dead after its step — the
@@ -1144,6 +1239,7 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       }
       lds_barrier();  // every read of both images done
       STAMP(stamp++);
+      }
     }
     if constexpr (XIN) {
       // in_proj outside: this tile's dZ_0 rows to HBM (feature k on the lane: 128-B row pieces)
@@ -1180,87 +1276,103 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
         lds_barrier();  // the next tile's Â^T planes are in place
       }
       STAMP(stamp++);
-    } else {
-    // in_proj: db_0, dW_0 += dZ_0^T X
-    {
-      const int K = a.width[0];
-      // (pipelined Â: unconditional — a branch around these barriers and stores made the
-      // register allocator spill ~116 VGPRs; past the last tile the planes written are unused)
-      if constexpr (AG && kAdjPipe) {
-        // the next tile's Â (issued at the last conv, long landed) and H_L rows: complete before
-        // the barrier below, so every wave can split the Â planes beside the dW_0 products
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (fresh_tid() == 0) sm.flag = 0;
-      }
-      {
-        const int tq = fresh_tid();
-        const int h = (tq >> 5) & 1, li = tq & 31, k = 32 * (tq >> 6) + li;
-        float sacc = 0.f;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc += dz[q][r];
-        sacc += __shfl_xor(sacc, 32, 64);
-        dbacc[0] += sacc;
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-          for (int gq = 0; gq < 4; ++gq) {
-            u32x2 o[3];
-            split4(f32x4{xp[q][4 * gq], xp[q][4 * gq + 1], xp[q][4 * gq + 2], xp[q][4 * gq + 3]},
-                   o);
-            const int off = hf_off(k, 32 * q + 8 * gq + 4 * h);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) sts8(sm.Img[p] + off, o[p]);
-          }
-        (void)K;
-        pre_cnt = (has_next && tq < TM) ? a.gptr[pre_g + 1] - a.gptr[pre_g] : 0;
-        if (has_head(a)) {
-#pragma unroll
-          for (int c = 0; c < kMaxHeadC; ++c)
-            pre_dl[c] = (has_next && tq < TM && c < a.C) ? head_raw(a, pre_g, c) : 0.f;
-          if (a.ce.pm) pre_wt = (has_next && tq < TM) ? a.ce.wt[pre_g] : 0.f;
-        }
-      }
-      lds_barrier();
-      AdjPlanes nap;  // the next tile's Â^T planes (pipe)
-      {
-        u32x4 gp[4][3];
-        split_p(dz, gp);
-        const int tq = fresh_tid();
-        const int h = (tq >> 5) & 1, li = tq & 31;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {  // node steps outer, as the conv layers' dW
-#pragma unroll
-          for (int kb = 0; kb < 4; ++kb) {
-            u32x4 hb[3];
-            const int off = hf_chunk(32 * kb + li, 2 * s + h);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) hb[p] = lds16(sm.Img[p] + off);
-            if constexpr (!(ABL & 1) && !XIN) dw[0][kb] = mfma_s3(gp[s], hb, dw[0][kb]);
-          }
-          // the next tile's Â split beside the products (independent VALU / LDS work)
-          if constexpr (AG && kAdjPipe) {
-            // (unconditional: without a next tile the planes are not written, and its flag
-            // word is never read)
-            if (s == 1) nap = adj_split(sm);
-          }
-          S3F_SB();
-        }
-      }
-      lds_barrier();  // X image read (and the Â scratch); the next tile may overwrite LDS
-      if constexpr (AG && kAdjPipe) {
-        adj_write(sm, nap);
-        lds_barrier();  // the next tile's Â^T planes are in place
-      }
-      STAMP(stamp++);
-    }
     }
     t = tn;
   }
   // partial slot blockIdx.x of every layer: dW rows n = 32 wave + (r & 3) + 8 (r >> 2) + 4h,
   // columns k = 32 kb + li; db from the h = 0 lanes
   if (write_slots) {
+    if constexpr (!XIN) {
+      // in_proj's partial from the folded sums, once per workgroup: dW_0 = W_1^T T and
+      // db_0 = W_1^T g, with T = sum over the tiles of G_1^T X (dw[0]: rows n of W_1, columns
+      // k of X) and g = sum of colsum G_1 (dbacc[0], lane n). T goes through LDS as a
+      // feature-major image [k][perm16 n] (128 rows of 256 B per plane: the H and G images'
+      // 96 KiB, free by now); A = W_1^T's planes (rows i = 32 wave + li, the dH operand), B = the
+      // image rows k = 32 kb + li, so the product lands in dW_0's accumulator layout. Widths
+      // below 128: the planes' zero padding and the masks of the slot write.
+      unsigned char* const timg = sm.Img[0];
+      constexpr int TPL = 2 * TM * AROW;  // bytes per plane of the T image
+      static_assert(3 * TPL == sizeof(sm.Img) + sizeof(sm.Gt) && offsetof(FBwdSmem, Gt) ==
+                                                                     sizeof(sm.Img), "T image");
+      float* const gl = sm.hl;
+      lds_barrier();  // (a workgroup without tiles: nothing pending; otherwise the tile's last)
+      {
+        const int tq = fresh_tid();
+        const int h = (tq >> 5) & 1, li = tq & 31, wv = tq >> 6;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+          for (int gq = 0; gq < 4; ++gq) {
+            u32x2 o3[3];
+            split4(f32x4{dw[0][kb][4 * gq], dw[0][kb][4 * gq + 1], dw[0][kb][4 * gq + 2],
+                         dw[0][kb][4 * gq + 3]}, o3);
+            const int off = ap_off(32 * kb + li, 32 * wv + 8 * gq + 4 * h);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) sts8(timg + p * TPL + off, o3[p]);
+          }
+        if (h == 0) gl[32 * wv + li] = dbacc[0];
+      }
+      lds_barrier();
+      {
+        const int tq = fresh_tid();
+        const int lane = tq & 63, h = lane >> 5, li = lane & 31, wv = tq >> 6;
+        const uint16_t* wbase = a.WpT + (size_t)3 * PLANE + wv * 8 * 512 + lane * 8;
+        // W_1^T planes two k-steps at a time, double-buffered (as the conv layers' dH loads them)
+        auto load_w2 = [&](u32x4 (&wf)[3][2], int pair) {
+#pragma unroll
+          for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int s2 = 0; s2 < 2; ++s2)
+              wf[p][s2] = (ABL & 16) ? u32x4{}
+                                     : *reinterpret_cast<const u32x4*>(wbase + p * PLANE +
+                                                                       512 * (2 * pair + s2));
+        };
+        u32x4 wa[3][2], wb[3][2];
+        load_w2(wa, 0);
+        load_w2(wb, 1);
+        float dbs = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) dw[0][kb] = f32x16{};
+        auto fold_pair = [&](const u32x4 (&wf)[3][2], int pair) {
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2) {
+            const int s = 2 * pair + s2;
+            // db_0[i] = sum_n W_1[n][i] g[n]: this lane's half of row i's positions (position
+            // 16 s + 8 h + e holds n = 16 s + perm16(8 h + e)), W_1 = hi + mid + lo
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              float wv3[3];
+#pragma unroll
+              for (int p = 0; p < 3; ++p)
+                wv3[p] = __uint_as_float((e & 1) ? wf[p][s2][e >> 1] & 0xffff0000u
+                                                 : wf[p][s2][e >> 1] << 16);
+              dbs += ((wv3[2] + wv3[1]) + wv3[0]) * gl[16 * s + perm16(8 * h + e)];
+            }
+            u32x4 aw[3];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) aw[p] = wf[p][s2];
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) {
+              u32x4 tb[3];
+              const int off = ap_chunk(32 * kb + li, 2 * s + h);
+#pragma unroll
+              for (int p = 0; p < 3; ++p) tb[p] = lds16(timg + p * TPL + off);
+              if constexpr (!(ABL & 1)) dw[0][kb] = mfma_s3(aw, tb, dw[0][kb]);
+            }
+            S3F_SB();
+          }
+        };
+        fold_pair(wa, 0);
+        load_w2(wa, 2);
+        fold_pair(wb, 1);
+        load_w2(wb, 3);
+        fold_pair(wa, 2);
+        fold_pair(wb, 3);
+        dbs += __shfl_xor(dbs, 32, 64);  // the partner half's positions
+        dbacc[0] = dbs;
+      }
+      STAMP(stamp++);
+    }
     const int tq = threadIdx.x;
     const int h = (tq >> 5) & 1, li = tq & 31, wv = tq >> 6;
 #pragma unroll

@@ -23,9 +23,15 @@ if os.environ.get("STAMPS_ABLATIONS"):
         VARIANTS[k] = [f"-DLGNN_ABLATE={v}"]
     VARIANTS["sb"] = ["-DLGNN_S3F_SB"]
     VARIANTS["sb_stamps"] = ["-DLGNN_S3F_SB", "-DLGNN_STAMPS"]
+# phases of one tile (L = 2). The first conv has in_proj folded behind it: no dH, one product
+# pass for dW_1 and T = G_1^T X with the next tile's Â split beside it; W_1^T T runs once per
+# workgroup after the last tile (the "fold + slots" span below)
 NAMES = ["prologue: stage + load wait", "prologue: dZ_L", "prologue: Â planes", "l2 G, G image",
-         "l2 H image", "l2 dW", "l2 dH+dZ", "l1 G, G image", "l1 H image", "l1 dW", "l1 dH+dZ",
-         "l0 X + dW", "tile tail"]
+         "l2 H image", "l2 dW", "l2 dH+dZ", "l1 G, X image", "l1 H image", "l1 dW + T, Â split",
+         "tile tail"]
+# the parent's phases (tools/build_base_lib.sh variants: in_proj as a per-tile phase of its own)
+NAMES_BASE = NAMES[:7] + ["l1 G, G image", "l1 H image", "l1 dW", "l1 dH+dZ", "l0 X + dW",
+                          "tile tail"]
 
 
 # variant libraries built from another source tree (tools/build_base_lib.sh: git HEAD's sources
@@ -102,12 +108,16 @@ def run():
             n = int((a[0, :62] > 0).sum())
             d = np.diff(a[:, :n], axis=1)
             print(f"stamps per block: {n}; mean span {(a[:, n - 1] - a[:, 0]).mean():.0f} ticks")
-            names = NAMES
+            names = NAMES_BASE if v.startswith("base") else NAMES
             per = len(names)
+            # the folded kernel stamps once more after W_1^T T, before the slot write
+            tail = (n - 1) % per == 0 and not v.startswith("base")
             for i in range(per):  # phases of the 2nd and later tiles, averaged
-                cols = [j for j in range(i, n - 1, per) if j >= per]
+                cols = [j for j in range(i, n - 1 - tail, per) if j >= per]
                 if cols:
                     print(f"{i:2d} {names[i]:22s} mean {d[:, cols].mean():8.0f}")
+            if tail:  # the last tile's tail (one barrier) + the fold, once per workgroup
+                print(f"   {'last tile tail + fold':22s} mean {d[:, n - 2].mean():8.0f}")
 
 
 if __name__ == "__main__":
