@@ -609,13 +609,44 @@ int lgnn_gcn_stack_bwd(const float* dP, const int64_t* batch, const int32_t* gpt
  *   incremented once, by the last one); ticket: device uint32[9], zero before the first call
  *   (re-armed by the call). Split a longer list over several calls with advance = 0 on all but
  *   the last (every call of one step then uses the same step count).
- *   Graph-capturable (lr and the betas are launch arguments: fixed in a captured graph).
+ *   Graph-capturable (lr and the betas are launch arguments: fixed in a captured graph; for a
+ *   rate that changes between replays see lgnn_adam_step_dlr).
  * ------------------------------------------------------------------------------------------- */
 int lgnn_adam_step(int n, float* const* params, const float* const* grads, float* const* exp_avg,
                    float* const* exp_avg_sq, const int64_t* numels, float* step,
                    unsigned int* ticket, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int decoupled, int maximize, int advance,
                    void* stream);
+
+/* lgnn_adam_step with the learning rate on the device: lr is a device float that every workgroup
+ * reads where it reads step[0], so a write to it between two replays of a captured graph (an LR
+ * scheduler's) acts on the next replay. Everything else is lgnn_adam_step's (one kernel body):
+ * given the same fp32 rate the two entries give bitwise equal results. lr = NULL: LGNN_EINVAL. */
+int lgnn_adam_step_dlr(int n, float* const* params, const float* const* grads,
+                       float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numels,
+                       float* step, unsigned int* ticket, const float* lr, float beta1,
+                       float beta2, float eps, float weight_decay, int decoupled, int maximize,
+                       int advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SGD step. Replaces: torch.optim.SGD as configured by the reference (models/base.py:162-188,
+ * OptimizerAlgo.SGD), in one launch over up to LGNN_MAX_ADAM fp32 tensors. Per element, in
+ * torch's order:
+ *   g = maximize ? -grad : grad;  g += weight_decay * p
+ *   momentum != 0: buf = (step == 0) ? g : momentum * buf + (1 - dampening) * g
+ *                  g = nesterov ? g + momentum * buf : buf
+ *   p -= lr * g
+ *   momentum_buf: one buffer per tensor; NULL allowed when momentum == 0 (never read then).
+ *   step / ticket: as for lgnn_adam_step (the first-step rule holds under replay); needed when
+ *   momentum != 0, ignored (NULL allowed) otherwise. advance as for lgnn_adam_step.
+ *   lr_dev (nullable): a device float; when given it is the rate and lr is not used.
+ *   nesterov needs momentum > 0 and dampening == 0 (LGNN_EINVAL otherwise, as torch raises).
+ * ------------------------------------------------------------------------------------------- */
+int lgnn_sgd_step(int n, float* const* params, const float* const* grads,
+                  float* const* momentum_buf, const int64_t* numels, float* step,
+                  unsigned int* ticket, float lr, const float* lr_dev, float momentum,
+                  float dampening, float weight_decay, int nesterov, int maximize, int advance,
+                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused GCN stack backward on split-3 bf16 MFMA (fp32 accuracy), every layer of a tile in one

@@ -218,18 +218,21 @@ class BaseModule(nn.Module):
             if st == stage:
                 ev.reset()
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, capturable: bool = False):
         """Reference base.py:162-188: the optimizer, plus a torch.optim.lr_scheduler by name or
-        pl_bolts' LinearWarmupCosineAnnealingLR (restated in lesion_gnn_amd.optim). Adam and
-        AdamW step in one HIP launch (lesion_gnn_amd.optim, same update as torch's)."""
+        pl_bolts' LinearWarmupCosineAnnealingLR (restated in lesion_gnn_amd.optim). Adam, AdamW
+        and SGD step in one HIP launch (lesion_gnn_amd.optim, same update as torch's).
+        capturable=True (the module already on the GPU) keeps the learning rate in a device
+        tensor, so the scheduler acts on the replays of a captured step."""
         from .. import optim as lgnn_optim
 
         ctor = {
             OptimizerAlgo.ADAM: lgnn_optim.Adam,
             OptimizerAlgo.ADAMW: lgnn_optim.AdamW,
-            OptimizerAlgo.SGD: torch.optim.SGD,
+            OptimizerAlgo.SGD: lgnn_optim.SGD,
         }[self.optimizer_algo]
-        optimizer = ctor(self.parameters(), lr=self.lr, weight_decay=self.weight_decay)
+        optimizer = ctor(self.parameters(), lr=self.lr, weight_decay=self.weight_decay,
+                         capturable=capturable)
         sc = self.lr_scheduler_config
         if sc is None:
             return optimizer
