@@ -839,10 +839,42 @@ int lgnn_sort_pool_bwd(const float* dout, const float* x, const int32_t* rank,
  *   [num_segments] int32 (nullable): pixels per label. 1 <= num_segments <= 4032. Workspace:
  *   lgnn_cc_pool_workspace_bytes. Two launches + two memsets, no host synchronisation.
  * ------------------------------------------------------------------------------------------- */
+#define LGNN_CC_POOL_MAX_SEGMENTS 4032
 size_t lgnn_cc_pool_workspace_bytes(int64_t num_pixels, int channels, int num_segments);
 int lgnn_cc_pool(const float* features, int channels, int64_t num_pixels, const int64_t* cc,
                  int num_segments, int reduce_max, float* out, int32_t* counts_out, int32_t* err,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Lesion nodes from a segmentation output. Replace: the argmax + adaptive max pool, the OpenCV
+ * connectedComponentsWithStats call and the host round trip between them (reference
+ * src/lesion_gnn/datasets/nodes/lesions.py:150-160). Images are row-major (height, width).
+ * lgnn_label_pool: logits [classes, in_height, in_width] fp32, 1 <= classes <= 255 -> out
+ *   [height, width] uint8 = adaptive_max_pool2d(argmax(logits, 0), (height, width)): the argmax
+ *   takes the first index among equal maxima; output row i covers input rows
+ *   [floor(i * in_height / height), ceil((i + 1) * in_height / height)), columns likewise (also
+ *   when height > in_height). One launch; the argmax map is never stored.
+ * lgnn_ccl: image [height, width] uint8, nonzero = foreground (pixels of different nonzero
+ *   values that touch are one component, OpenCV's rule); connectivity 4 or 8. labels
+ *   [height * width] int64: 0 for the background (also when the image has none), components
+ *   numbered 1, 2, ... in raster order of their first pixel (smallest y * width + x:
+ *   scipy.ndimage.label's numbering, a pure function of the image). num_labels [1] int32 on the
+ *   device: components + 1. Workspace: lgnn_ccl_workspace_bytes(height, width) (0 for sizes the
+ *   entry refuses). height * width < 2^31. Six launches, no host synchronisation, no workgroup
+ *   waits on another.
+ * lgnn_ccl_stats: labels [height * width] int64 in [0, num_labels) -> stats [num_labels, 5]
+ *   int32 (left, top, width, height, area: OpenCV's columns; row 0 is the background's) and
+ *   centroids [num_labels, 2] fp64 (mean x, mean y) = double(integer sum) / double(area). A
+ *   label without a pixel gets zeros in both. Labels outside the range are skipped and counted
+ *   in *err (written). Three launches.
+ * ------------------------------------------------------------------------------------------- */
+int lgnn_label_pool(const float* logits, int classes, int in_height, int in_width, uint8_t* out,
+                    int height, int width, void* stream);
+size_t lgnn_ccl_workspace_bytes(int height, int width);
+int lgnn_ccl(const uint8_t* image, int height, int width, int connectivity, int64_t* labels,
+             int32_t* num_labels, void* workspace, size_t workspace_bytes, void* stream);
+int lgnn_ccl_stats(const int64_t* labels, int height, int width, int num_labels, int32_t* stats,
+                   double* centroids, int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * bf16 dense GEMMs (bf16 GEMM operands rounded round-to-nearest-even as torch's

@@ -45,7 +45,7 @@ _ANY = frozenset(v for v in vars(torch).values() if isinstance(v, torch.dtype))
 _POINTEE_DTYPES = {
     "float": frozenset({torch.float32}), "double": frozenset({torch.float64}),
     "int32_t": _INT4, "int": _INT4, "unsigned int": _INT4, "uint32_t": _INT4,
-    "int64_t": _INT8, "uint64_t": _INT8,
+    "int64_t": _INT8, "uint64_t": _INT8, "uint8_t": frozenset({torch.uint8}),
     "uint16_t": frozenset({torch.int16, torch.uint16, torch.bfloat16}),  # the bf16 planes
     "void": _ANY,
 }

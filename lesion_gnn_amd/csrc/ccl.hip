@@ -1,0 +1,497 @@
+// Lesion nodes from a segmentation output: class map, connected components, component statistics.
+// Reference: src/lesion_gnn/datasets/nodes/lesions.py:150-160 — torch.argmax +
+// F.adaptive_max_pool2d on the GPU, .byte().cpu().numpy(), then
+// cv2.connectedComponentsWithStatsWithAlgorithm(connectivity=8) on the host and the labels copied
+// back. Here the chain stays on the device.
+//
+// k_label_pool  — one thread per output pixel: the argmax over the classes of every input pixel
+//                 of its pooling window (first index among equal maxima), the largest of them.
+// Labelling (lgnn_ccl) is a union-find over an int32 parent word per pixel (background -1), in
+// which a parent is never larger than its child: the root of a component is its first pixel in
+// raster order, so ranking the roots numbers the components as the contract asks.
+// k_ccl_init    — a wave takes 64 consecutive pixels of a row: one ballot gives every lane the
+//                 start of its run inside the segment, which becomes its parent. No atomics.
+// k_ccl_merge   — the links the init left out: a run continuing across a segment border, and the
+//                 row above (N, or NW / NE where N is background; a pixel whose left neighbour is
+//                 foreground leaves to it what that neighbour already links). Unions by atomicMin
+//                 on the larger root, retried with the value the atomic returned; every parent
+//                 word is read with an agent-scope atomic load (another workgroup, possibly on
+//                 another XCD, may be changing it).
+// k_ccl_compress— every pixel's parent becomes its root; roots counted per 1024-pixel block.
+// k_ccl_scan    — one workgroup: exclusive scan of the block counts, num_labels.
+// k_ccl_rank    — root -> 1 + its rank among the roots.
+// k_ccl_label   — labels[p] = rank of the root of p.
+// The phases are separate launches: no workgroup waits on another inside one.
+// Statistics (lgnn_ccl_stats): integer min / max / count / coordinate sums per label. A lane walks
+// 8 consecutive pixels and keeps one (label, partial) run in registers; a run goes to the
+// workgroup's LDS bins (labels below 1024: the background, which holds most pixels of a lesion
+// map, is label 0) or, above, to global memory; the touched bins leave as one global integer
+// atomic each. Integer sums: any order gives the same bits.
+#include <algorithm>
+#include <climits>
+
+#include "common.h"
+
+namespace lgnn_cclk {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kSeg = 64;        // pixels of one row per wave (init, merge)
+constexpr int kScanPix = 1024;  // pixels per workgroup (compress, rank): 4 per thread
+constexpr int kScanThreads = 1024;
+constexpr int kBins = 1024;     // labels with LDS bins (stats)
+constexpr int kRun = 8;         // consecutive pixels per lane (stats)
+
+__global__ void __launch_bounds__(kThreads)
+    k_label_pool(const float* __restrict__ logits, int K, int Hin, int Win,
+                 uint8_t* __restrict__ out, int H, int W) {
+  const int64_t o = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (o >= (int64_t)H * W) return;
+  const int oy = (int)(o / W), ox = (int)(o - (int64_t)oy * W);
+  const int y0 = (int)((int64_t)oy * Hin / H), y1 = (int)(((int64_t)(oy + 1) * Hin + H - 1) / H);
+  const int x0 = (int)((int64_t)ox * Win / W), x1 = (int)(((int64_t)(ox + 1) * Win + W - 1) / W);
+  const int64_t plane = (int64_t)Hin * Win;
+  int best = 0;
+  for (int y = y0; y < y1; ++y)
+    for (int x = x0; x < x1; ++x) {
+      const float* q = logits + (int64_t)y * Win + x;
+      float m = q[0];
+      int a = 0;
+      for (int k = 1; k < K; ++k) {
+        const float v = q[k * plane];
+        if (v > m || (v != v && m == m)) {  // torch.argmax: a NaN is the maximum, the first wins
+          m = v;
+          a = k;
+        }
+      }
+      best = max(best, a);
+    }
+  out[o] = (uint8_t)best;
+}
+
+__device__ __forceinline__ int32_t ld_agent(const int32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// parent[x] <= x for every x at all times, so the walk strictly descends until a fixed point.
+// A value read late is still an ancestor of x: parents are only ever replaced by smaller members
+// of the same component.
+__device__ __forceinline__ int32_t find_root(const int32_t* parent, int32_t x) {
+  int32_t p = ld_agent(parent + x);
+  while (p != x) {
+    x = p;
+    p = ld_agent(parent + x);
+  }
+  return x;
+}
+
+// The same walk in the merge launch, where it also points every node it passes at its grandparent
+// (an ancestor, and smaller: still a decrease), so that the links of a long run's segments, made
+// one by one, do not grow into a chain every later walk follows to its end.
+__device__ __forceinline__ int32_t find_root_split(int32_t* parent, int32_t x) {
+  int32_t p = ld_agent(parent + x);
+  while (p != x) {
+    const int32_t g = ld_agent(parent + p);
+    if (g != p) atomicMin(parent + x, g);
+    x = p;
+    p = g;
+  }
+  return x;
+}
+
+// Link the components of a and b. The atomicMin either finds the larger root still a root (done)
+// or returns the smaller parent another lane gave it; the retry starts from that value. max(a, b)
+// strictly decreases from one iteration to the next, so the loop ends.
+__device__ __forceinline__ void unite(int32_t* parent, int32_t a, int32_t b) {
+  for (;;) {
+    a = find_root_split(parent, a);
+    b = find_root_split(parent, b);
+    if (a == b) return;
+    if (a < b) {
+      const int32_t t = a;
+      a = b;
+      b = t;
+    }
+    const int32_t old = atomicMin(parent + a, b);
+    if (old == a) return;
+    a = old;
+  }
+}
+
+// wave -> (row y, 64-pixel segment of it); false past the image (wave-uniform)
+__device__ __forceinline__ bool seg_task(int H, int nseg, int& y, int& x0) {
+  const int64_t task = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (task >= (int64_t)H * nseg) return false;
+  y = (int)(task / nseg);
+  x0 = (int)(task - (int64_t)y * nseg) * kSeg;
+  return true;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    k_ccl_init(const uint8_t* __restrict__ img, int H, int W, int nseg,
+               int32_t* __restrict__ parent) {
+  int y, x0;
+  if (!seg_task(H, nseg, y, x0)) return;
+  const int lane = threadIdx.x & 63, x = x0 + lane;
+  const bool fg = x < W && img[(int64_t)y * W + x] != 0;
+  const unsigned long long mask = __ballot(fg);
+  if (x >= W) return;
+  // the run of lane starts one past the highest background lane below it
+  const unsigned long long below = ~mask & ((1ull << lane) - 1ull);
+  const int start = below ? 64 - __clzll(below) : 0;
+  parent[y * W + x] = fg ? y * W + x0 + start : -1;
+}
+
+template <bool k8>
+__global__ void __launch_bounds__(kThreads)
+    k_ccl_merge(const uint8_t* __restrict__ img, int H, int W, int nseg, int32_t* parent) {
+  int y, x0;
+  if (!seg_task(H, nseg, y, x0)) return;
+  const int lane = threadIdx.x & 63, x = x0 + lane;
+  const bool fg = x < W && img[(int64_t)y * W + x] != 0;
+  const unsigned long long mask = __ballot(fg);
+  if (!fg) return;
+  const int p = y * W + x;
+  bool left;
+  if (lane > 0) {
+    left = (mask >> (lane - 1)) & 1ull;
+  } else {
+    left = x > 0 && img[(int64_t)p - 1] != 0;
+    if (left) unite(parent, p, p - 1);  // the run continues across the segment border
+  }
+  if (y == 0) return;
+  const uint8_t* up = img + (int64_t)(y - 1) * W;
+  const bool n = up[x] != 0;
+  // By induction along a row's run, a pixel ends up linked to every foreground pixel among its
+  // W, NW, N, NE (8) or W, N (4): the run's first pixel links them itself (through N where N is
+  // foreground: NW and NE touch N in the row above); a later pixel gets NW and N through its left
+  // neighbour, whose N and NE they are, and links NE itself only where N does not carry it.
+  if (k8) {
+    const bool ne = x + 1 < W && up[x + 1] != 0;
+    if (left) {
+      if (!n && ne) unite(parent, p, p - W + 1);
+    } else if (n) {
+      unite(parent, p, p - W);
+    } else {
+      if (x > 0 && up[x - 1] != 0) unite(parent, p, p - W - 1);
+      if (ne) unite(parent, p, p - W + 1);
+    }
+  } else {
+    // 4: N is reached through the left neighbour when that one's own N is foreground too
+    if (n && !(left && up[x - 1] != 0)) unite(parent, p, p - W);
+  }
+}
+
+// sum of v over the workgroup (every thread gets it); kThreads threads
+__device__ __forceinline__ int block_sum(int v, int32_t* wsum) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int s = 0;
+  for (int w = 0; w < kWaves; ++w) s += wsum[w];
+  return s;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    k_ccl_compress(int32_t* parent, int64_t npix, int32_t* __restrict__ blockcount) {
+  __shared__ int32_t wsum[kWaves];
+  const int64_t base = (int64_t)blockIdx.x * kScanPix + threadIdx.x * 4;
+  int c = 0;
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = base + j;
+    if (p >= npix) break;
+    const int32_t q = ld_agent(parent + p);
+    if (q < 0) continue;
+    const int32_t r = find_root(parent, q);
+    // roots are final since the merge launch ended; a concurrent walk through p reads the old
+    // parent or the root, both ancestors
+    if (r != q) __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c += r == (int32_t)p;
+  }
+  const int s = block_sum(c, wsum);
+  if (threadIdx.x == 0) blockcount[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(kScanThreads)
+    k_ccl_scan(int32_t* __restrict__ blockcount, int nb, int32_t* __restrict__ num_labels) {
+  __shared__ int32_t wsum[kScanThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int carry = 0;
+  for (int base = 0; base < nb; base += kScanThreads) {
+    const int i = base + threadIdx.x;
+    const int v = i < nb ? blockcount[i] : 0;
+    int s = v;
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(s, o, 64);
+      if (lane >= o) s += t;
+    }
+    if (lane == 63) wsum[wave] = s;
+    __syncthreads();
+    int woff = 0, total = 0;
+    for (int w = 0; w < kScanThreads / 64; ++w) {
+      if (w < wave) woff += wsum[w];
+      total += wsum[w];
+    }
+    if (i < nb) blockcount[i] = carry + woff + s - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *num_labels = carry + 1;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    k_ccl_rank(const int32_t* __restrict__ parent, int64_t npix,
+               const int32_t* __restrict__ blockoff, int32_t* __restrict__ rootlabel) {
+  __shared__ int32_t wsum[kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t base = (int64_t)blockIdx.x * kScanPix + threadIdx.x * 4;
+  bool root[4];
+  int c = 0;
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = base + j;
+    root[j] = p < npix && parent[p] == (int32_t)p;
+    c += root[j];
+  }
+  int s = c;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(s, o, 64);
+    if (lane >= o) s += t;
+  }
+  if (lane == 63) wsum[wave] = s;
+  __syncthreads();
+  int r = blockoff[blockIdx.x] + s - c + 1;
+  for (int w = 0; w < wave; ++w) r += wsum[w];
+  for (int j = 0; j < 4; ++j)
+    if (root[j]) rootlabel[base + j] = r++;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    k_ccl_label(const int32_t* __restrict__ parent, const int32_t* __restrict__ rootlabel,
+                int64_t npix, int64_t* __restrict__ labels) {
+  const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (p >= npix) return;
+  const int32_t q = parent[p];
+  labels[p] = q < 0 ? 0 : rootlabel[q];
+}
+
+// ---- statistics ------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads)
+    k_stats_init(int n, int32_t* __restrict__ stats, unsigned long long* __restrict__ sums,
+                 int32_t* __restrict__ err) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i == 0) *err = 0;
+  if (i >= n) return;
+  int32_t* s = stats + (int64_t)i * 5;
+  s[0] = INT_MAX;  // min x
+  s[1] = INT_MAX;  // min y
+  s[2] = -1;       // max x, the width once finished
+  s[3] = -1;       // max y, the height once finished
+  s[4] = 0;
+  sums[2 * (int64_t)i] = 0ull;
+  sums[2 * (int64_t)i + 1] = 0ull;
+}
+
+__global__ void __launch_bounds__(kThreads)
+    k_stats_acc(const int64_t* __restrict__ labels, int64_t npix, int W, int n, int chunks,
+                int32_t* __restrict__ stats, unsigned long long* __restrict__ sums,
+                int32_t* __restrict__ err) {
+  __shared__ int32_t b_minx[kBins], b_miny[kBins], b_maxx[kBins], b_maxy[kBins], b_area[kBins];
+  __shared__ unsigned long long b_sx[kBins], b_sy[kBins];
+  const int nb = min(n, kBins);
+  for (int i = threadIdx.x; i < nb; i += kThreads) {
+    b_minx[i] = INT_MAX;
+    b_miny[i] = INT_MAX;
+    b_maxx[i] = -1;
+    b_maxy[i] = -1;
+    b_area[i] = 0;
+    b_sx[i] = 0ull;
+    b_sy[i] = 0ull;
+  }
+  __syncthreads();
+
+  int bad = 0;
+  for (int c = 0; c < chunks; ++c) {
+    const int64_t p0 =
+        ((int64_t)blockIdx.x * chunks + c) * (kThreads * kRun) + (int64_t)threadIdx.x * kRun;
+    if (p0 >= npix) break;
+    int y = (int)(p0 / W), x = (int)(p0 - (int64_t)y * W);
+    int cur = -1, minx = 0, maxx = 0, miny = 0, maxy = 0, area = 0;
+    unsigned long long sx = 0ull, sy = 0ull;
+    auto flush = [&]() {
+      if (cur < 0) return;
+      if (cur < nb) {
+        atomicMin(&b_minx[cur], minx);
+        atomicMin(&b_miny[cur], miny);
+        atomicMax(&b_maxx[cur], maxx);
+        atomicMax(&b_maxy[cur], maxy);
+        atomicAdd(&b_area[cur], area);
+        atomicAdd(&b_sx[cur], sx);
+        atomicAdd(&b_sy[cur], sy);
+      } else {
+        int32_t* s = stats + (int64_t)cur * 5;
+        atomicMin(s + 0, minx);
+        atomicMin(s + 1, miny);
+        atomicMax(s + 2, maxx);
+        atomicMax(s + 3, maxy);
+        atomicAdd(s + 4, area);
+        atomicAdd(sums + 2 * (int64_t)cur, sx);
+        atomicAdd(sums + 2 * (int64_t)cur + 1, sy);
+      }
+    };
+    const int m = (int)min((int64_t)kRun, npix - p0);
+    for (int j = 0; j < m; ++j) {
+      const int64_t l = labels[p0 + j];
+      if (l < 0 || l >= n) {
+        ++bad;
+      } else if ((int)l != cur) {
+        flush();
+        cur = (int)l;
+        minx = maxx = x;
+        miny = maxy = y;
+        area = 1;
+        sx = (unsigned long long)x;
+        sy = (unsigned long long)y;
+      } else {
+        minx = min(minx, x);
+        maxx = max(maxx, x);
+        maxy = y;  // rows only grow along a lane's pixels
+        ++area;
+        sx += (unsigned long long)x;
+        sy += (unsigned long long)y;
+      }
+      if (++x == W) {
+        x = 0;
+        ++y;
+      }
+    }
+    flush();
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb; i += kThreads) {
+    if (!b_area[i]) continue;
+    int32_t* s = stats + (int64_t)i * 5;
+    atomicMin(s + 0, b_minx[i]);
+    atomicMin(s + 1, b_miny[i]);
+    atomicMax(s + 2, b_maxx[i]);
+    atomicMax(s + 3, b_maxy[i]);
+    atomicAdd(s + 4, b_area[i]);
+    atomicAdd(sums + 2 * (int64_t)i, b_sx[i]);
+    atomicAdd(sums + 2 * (int64_t)i + 1, b_sy[i]);
+  }
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(err, bad);
+}
+
+// the integer sums sit in the centroid words; each label's thread reads both before it writes
+__global__ void __launch_bounds__(kThreads)
+    k_stats_finish(int n, int32_t* __restrict__ stats, double* centroids) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  int32_t* s = stats + (int64_t)i * 5;
+  const unsigned long long* sums = reinterpret_cast<const unsigned long long*>(centroids);
+  const unsigned long long sx = sums[2 * (int64_t)i], sy = sums[2 * (int64_t)i + 1];
+  const int area = s[4];
+  if (area == 0) {
+    s[0] = s[1] = s[2] = s[3] = 0;
+    centroids[2 * (int64_t)i] = 0.0;
+    centroids[2 * (int64_t)i + 1] = 0.0;
+    return;
+  }
+  s[2] = s[2] - s[0] + 1;
+  s[3] = s[3] - s[1] + 1;
+  centroids[2 * (int64_t)i] = (double)(long long)sx / (double)area;
+  centroids[2 * (int64_t)i + 1] = (double)(long long)sy / (double)area;
+}
+
+}  // namespace lgnn_cclk
+
+using namespace lgnn_cclk;
+
+static bool image_dims_ok(int H, int W) {
+  return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31);
+}
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+extern "C" int lgnn_label_pool(const float* logits, int classes, int in_height, int in_width,
+                               uint8_t* out, int height, int width, void* stream) {
+  if (classes < 1 || classes > 255 || !image_dims_ok(in_height, in_width) ||
+      !image_dims_ok(height, width) || !logits || !out)
+    return LGNN_EINVAL;
+  const int64_t npix = (int64_t)height * width;
+  hipLaunchKernelGGL(k_label_pool, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, as_stream(stream), logits, classes, in_height, in_width,
+                     out, height, width);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" size_t lgnn_ccl_workspace_bytes(int height, int width) {
+  if (!image_dims_ok(height, width)) return 0;
+  const int64_t npix = (int64_t)height * width;
+  const int64_t nb = (npix + kScanPix - 1) / kScanPix;
+  return 2 * align256((size_t)npix * sizeof(int32_t)) + align256((size_t)nb * sizeof(int32_t));
+}
+
+extern "C" int lgnn_ccl(const uint8_t* image, int height, int width, int connectivity,
+                        int64_t* labels, int32_t* num_labels, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  if ((connectivity != 4 && connectivity != 8) || !image_dims_ok(height, width)) return LGNN_EINVAL;
+  if (!image || !labels || !num_labels || !workspace ||
+      workspace_bytes < lgnn_ccl_workspace_bytes(height, width))
+    return LGNN_EINVAL;
+  hipStream_t s = as_stream(stream);
+  const int64_t npix = (int64_t)height * width;
+  const int nb = (int)((npix + kScanPix - 1) / kScanPix);
+  char* ws = static_cast<char*>(workspace);
+  int32_t* parent = reinterpret_cast<int32_t*>(ws);
+  ws += align256((size_t)npix * sizeof(int32_t));
+  int32_t* rootlabel = reinterpret_cast<int32_t*>(ws);
+  ws += align256((size_t)npix * sizeof(int32_t));
+  int32_t* blockcount = reinterpret_cast<int32_t*>(ws);
+
+  const int nseg = (width + kSeg - 1) / kSeg;
+  const dim3 sgrid((unsigned)(((int64_t)height * nseg + kWaves - 1) / kWaves));
+  hipLaunchKernelGGL(k_ccl_init, sgrid, dim3(kThreads), 0, s, image, height, width, nseg, parent);
+  LGNN_LAUNCH_CHECK();
+  if (connectivity == 8)
+    hipLaunchKernelGGL(k_ccl_merge<true>, sgrid, dim3(kThreads), 0, s, image, height, width, nseg,
+                       parent);
+  else
+    hipLaunchKernelGGL(k_ccl_merge<false>, sgrid, dim3(kThreads), 0, s, image, height, width,
+                       nseg, parent);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_compress, dim3(nb), dim3(kThreads), 0, s, parent, npix, blockcount);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_scan, dim3(1), dim3(kScanThreads), 0, s, blockcount, nb, num_labels);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_rank, dim3(nb), dim3(kThreads), 0, s, parent, npix, blockcount,
+                     rootlabel);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_label, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, s, parent, rootlabel, npix, labels);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" int lgnn_ccl_stats(const int64_t* labels, int height, int width, int num_labels,
+                              int32_t* stats, double* centroids, int32_t* err, void* stream) {
+  if (!image_dims_ok(height, width) || num_labels < 1) return LGNN_EINVAL;
+  if (!labels || !stats || !centroids || !err) return LGNN_EINVAL;
+  hipStream_t s = as_stream(stream);
+  const int64_t npix = (int64_t)height * width;
+  unsigned long long* sums = reinterpret_cast<unsigned long long*>(centroids);
+  const dim3 lgrid((unsigned)((num_labels + kThreads - 1) / kThreads));
+  hipLaunchKernelGGL(k_stats_init, lgrid, dim3(kThreads), 0, s, num_labels, stats, sums, err);
+  LGNN_LAUNCH_CHECK();
+  const int64_t chunk = (int64_t)kThreads * kRun;
+  const int64_t nchunks = (npix + chunk - 1) / chunk;
+  const int grid = (int)std::min<int64_t>(nchunks, 1024);
+  const int chunks = (int)((nchunks + grid - 1) / grid);
+  hipLaunchKernelGGL(k_stats_acc, dim3(grid), dim3(kThreads), 0, s, labels, npix, width,
+                     num_labels, chunks, stats, sums, err);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_stats_finish, lgrid, dim3(kThreads), 0, s, num_labels, stats, centroids);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}

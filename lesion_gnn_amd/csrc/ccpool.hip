@@ -22,7 +22,7 @@ namespace lgnn_ccpool {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxSeg = 4032;        // 4 wave-private bin arrays (< 64 KB of LDS)
+constexpr int kMaxSeg = LGNN_CC_POOL_MAX_SEGMENTS;  // 4032: 4 wave-private bin arrays (< 64 KB of LDS)
 constexpr int64_t kSlicePix = 65536; // pixels per workgroup slice
 
 __device__ __forceinline__ int32_t f2ord(float f) {

@@ -1,2 +1,3 @@
-"""Node-extractor configs (reference src/lesion_gnn/datasets/nodes) and the per-component
-feature pooling kernel (lesions.extract_features_by_cc)."""
+"""Node-extractor configs (reference src/lesion_gnn/datasets/nodes) and the lesion-node extraction
+from a segmentation output on HIP kernels (lesions.LesionsExtractor.nodes_from_maps,
+lesions.connected_components_with_stats, lesions.extract_features_by_cc)."""

@@ -1,11 +1,15 @@
-"""Lesion-node extractor configuration (reference src/lesion_gnn/datasets/nodes/lesions.py:
-22-71: the feature sources, `FeaturesReduction`, `LesionsNodesConfig`).
+"""Lesion-node extraction (reference src/lesion_gnn/datasets/nodes/lesions.py): the
+configuration (:22-71: the feature sources, `FeaturesReduction`, `LesionsNodesConfig`) and the
+extractor from the segmentation output on (:147-177).
 
-The extractor itself (`LesionsExtractor.__call__`, :111-177: fundus segmentation, a timm encoder
-from the HF hub, OpenCV connected components) needs network weights and image data and is out
-of scope; its per-component feature pooling `extract_features_by_cc` (:88-93,
-called at :172) is the scatter that produces the d_in = encoder channels + 1 node features, and
-runs here on the HIP kernel lgnn_cc_pool.
+The front of `LesionsExtractor.__call__` (:111-145: image loading, the fundus segmentation model,
+a timm encoder from the HF hub) needs network weights and image data and is out of scope
+(DESIGN.md §7). What follows it starts from two tensors and runs on HIP kernels:
+`nodes_from_maps` pools the argmax of the segmentation logits to the feature size
+(lgnn_label_pool), labels its connected components and takes their centroids (lgnn_ccl,
+lgnn_ccl_stats: `connected_components_with_stats`, in place of OpenCV on the host), and pools
+the features per component (`extract_features_by_cc`, :88-93, lgnn_cc_pool) into the d_in =
+encoder channels + 1 node features.
 """
 from __future__ import annotations
 
@@ -68,3 +72,97 @@ def extract_features_by_cc(cc: torch.Tensor, features: torch.Tensor, nlabel: int
         return ops.cc_pool(f, torch.zeros_like(cc), 1, reduce_max=False).view(1, C)
     size = int(cc.max().item()) + 1
     return ops.cc_pool(f, cc, size, reduce_max=(reduce == "max"))
+
+
+def connected_components_with_stats(image: torch.Tensor, connectivity: int = 8):
+    """cv2.connectedComponentsWithStats on the GPU (reference lesions.py:158-160): image (H, W),
+    nonzero = foreground, cast as the reference's `.byte()` does -> (nlabel: int, cc (H, W)
+    int64, stats (nlabel, 5) int32: left, top, width, height, area, centroids (nlabel, 2) fp64:
+    x, y), tensors on the device. Label 0 is the background; components are numbered in raster
+    order of their first pixel (scipy.ndimage.label's order; OpenCV's may be a permutation of
+    it). One host read: nlabel, which sizes the outputs."""
+    from ... import ops
+
+    if image.dim() != 2:
+        raise ValueError("image must be (H, W)")
+    img = image if image.dtype == torch.uint8 else image.to(torch.uint8)
+    cc, num = ops.ccl(img, connectivity)
+    nlabel = int(num.item())
+    stats, centroids = ops.ccl_stats(cc, nlabel, validate=False)
+    return nlabel, cc, stats, centroids
+
+
+@dataclasses.dataclass
+class LesionNodes:
+    """The graph of one image before its edges exist: the attributes of the reference's
+    `Data(pos, y, name, x)` (lesions.py:174-176) that KNNGraph, RadiusGraph and GaussianDistance
+    read and write."""
+
+    pos: torch.Tensor  # [n, 2] fp64 (x, y) in the coordinates of the segmentation output
+    x: torch.Tensor    # [n, C + 1] fp32: pooled features, then the pooled class
+    y: torch.Tensor    # tensor([label])
+    name: str | None = None
+    edge_index: torch.Tensor | None = None
+    edge_attr: torch.Tensor | None = None
+
+
+class LesionsExtractor:
+    """Reference LesionsExtractor (lesions.py:96-186) from the segmentation output on:
+    `nodes_from_maps` is lines 147-176 on the GPU. The segmentation model, the timm encoder and
+    image loading are not part of this package, so `__call__` raises."""
+
+    def __init__(self, config: LesionsNodesConfig):
+        self.feature_source = config.feature_source
+        self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
+        self.features_reduction = FeaturesReduction(config.features_reduction)
+        self.reinterpolation = config.reinterpolation
+        # config.compile wraps the scatter in torch.compile in the reference; the HIP launches
+        # here have nothing to compile, so it is accepted and ignored
+
+    def __call__(self, img_path, label: int):
+        raise NotImplementedError(
+            "LesionsExtractor.__call__ needs the fundus segmentation model and image loading, "
+            "which are outside this package: run them and pass their outputs to "
+            "nodes_from_maps(label_map, features, label, name)")
+
+    @torch.no_grad()
+    def nodes_from_maps(self, label_map: torch.Tensor, features: torch.Tensor, label: int,
+                        name: str | None = None) -> LesionNodes:
+        """label_map (1, K, Horg, Worg) fp32 segmentation logits and features (1, C, h, w) fp32,
+        both on the GPU -> the image's lesion nodes (the background's included, as in the
+        reference): one node per connected component of the nonzero classes at the feature
+        resolution, its centroid scaled back by Horg / H and its mean / max feature with the
+        class appended."""
+        from ... import _lib, ops
+
+        _lib.require_gpu(label_map, features)
+        if label_map.dim() != 4 or label_map.size(0) != 1:
+            raise ValueError("label_map must be (1, K, H, W)")
+        if features.dim() != 4 or features.size(0) != 1:
+            raise ValueError("features must be (1, C, H, W)")
+        if self.reinterpolation is not None:
+            features = torch.nn.functional.interpolate(
+                features, size=self.reinterpolation, mode="bilinear", align_corners=False)
+        Horg = label_map.size(2)
+        C, H, W = features.shape[1:]
+        classes = ops.label_pool(label_map[0], (H, W))
+        nlabel, cc, _, centroids = connected_components_with_stats(classes, connectivity=8)
+        limit = _lib.LGNN_CC_POOL_MAX_SEGMENTS
+        if nlabel > limit:
+            raise ValueError(f"{nlabel} components (background included) exceed the {limit} "
+                             "segments lgnn_cc_pool takes")
+        # (centroids * Horg) / H as numpy rounds it: a tensor divisor, since torch divides a GPU
+        # tensor by a Python number as a product with the rounded reciprocal
+        centroids = (centroids * Horg) / torch.full_like(centroids, H)
+        # pooling is per channel, so the class channel is pooled on its own instead of through a
+        # copy of the whole feature map with one channel appended (reference :169)
+        reduce_max = self.features_reduction == FeaturesReduction.MAX and nlabel > 1
+        lab = cc.reshape(-1)
+        x = torch.cat([
+            ops.cc_pool(features.reshape(C, H * W), lab, nlabel, reduce_max, validate=False),
+            ops.cc_pool(classes.reshape(1, H * W).float(), lab, nlabel, reduce_max,
+                        validate=False)], dim=1)
+        return LesionNodes(pos=centroids, x=x, y=torch.tensor([label]), name=name)
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}(feature_source={self.feature_source})"

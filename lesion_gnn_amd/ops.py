@@ -2187,6 +2187,63 @@ def cc_pool(features: torch.Tensor, cc: torch.Tensor, num_segments: int, reduce_
     return out
 
 
+def label_pool(logits: torch.Tensor, size: tuple[int, int]) -> torch.Tensor:
+    """logits (K, Hin, Win) fp32, K <= 255 -> (H, W) uint8 class map equal to
+    F.adaptive_max_pool2d(argmax(logits, 0).float(), size), in one launch (lgnn_label_pool)."""
+    _lib.require_gpu(logits)
+    if logits.dim() != 3:
+        raise ValueError("logits must be (K, H, W)")
+    f = _f32c(logits)
+    K, Hin, Win = f.shape
+    if not 1 <= K <= 255:
+        raise ValueError("label_pool takes 1 to 255 classes")
+    H, W = int(size[0]), int(size[1])
+    out = torch.empty(H, W, dtype=torch.uint8, device=f.device)
+    _lib.call("lgnn_label_pool", f, K, Hin, Win, out, H, W, _s(f.device))
+    return out
+
+
+def ccl(image: torch.Tensor, connectivity: int = 8) -> tuple[torch.Tensor, torch.Tensor]:
+    """image (H, W) uint8, nonzero = foreground -> (labels (H, W) int64, num_labels int32 [1] on
+    the device, background included): 0 the background, components 1, 2, ... in raster order of
+    their first pixel (lgnn_ccl). No host synchronisation."""
+    _lib.require_gpu(image)
+    if image.dim() != 2 or image.dtype != torch.uint8:
+        raise ValueError("image must be a (H, W) uint8 tensor")
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    img = image.contiguous()
+    H, W = img.shape
+    dev = img.device
+    labels = torch.empty(H, W, dtype=torch.int64, device=dev)
+    num = torch.empty(1, dtype=torch.int32, device=dev)
+    nws = _lib.load().lgnn_ccl_workspace_bytes(H, W)
+    ws = torch.empty(max(1, nws), dtype=torch.uint8, device=dev)
+    _lib.call("lgnn_ccl", img, H, W, int(connectivity), labels, num, ws, nws, _s(dev))
+    return labels, num
+
+
+def ccl_stats(labels: torch.Tensor, num_labels: int,
+              validate: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """labels (H, W) int64 in [0, num_labels) -> (stats (num_labels, 5) int32: left, top, width,
+    height, area; centroids (num_labels, 2) fp64: mean x, mean y) (lgnn_ccl_stats). validate:
+    raise if a label falls outside the range (one host read)."""
+    _lib.require_gpu(labels)
+    if labels.dim() != 2 or labels.dtype != torch.int64:
+        raise ValueError("labels must be a (H, W) int64 tensor")
+    lab = labels.contiguous()
+    H, W = lab.shape
+    dev = lab.device
+    n = int(num_labels)
+    stats = torch.empty(n, 5, dtype=torch.int32, device=dev)
+    centroids = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_ccl_stats", lab, H, W, n, stats, centroids, err, _s(dev))
+    if validate and int(err.item()):
+        raise IndexError(f"ccl_stats: {int(err.item())} labels outside [0, {n})")
+    return stats, centroids
+
+
 # ----------------------------------------------------------------------------------------------
 # Set attention (setattn.hip): segmented multi-head attention over ragged sets, the residual +
 # activation + LayerNorm of PyG's MultiheadAttentionBlock, the set readout
