@@ -266,7 +266,9 @@ int lgnn_node_linear_bwd(int grad_mode, const float* dY, const int64_t* batch, c
  * overwriting it, and a workgroup that processed none leaves its slot alone. accumulate = 2 (after
  * lgnn_gcn_stack_bwd_s3f, num_partials <= LGNN_SLOT_FLAGS): the same, except for slots whose skip
  * word in tile_open is set (the fused kernel wrote nothing there): those are written, with zeros
- * by a workgroup that processed no tile. Fast path only. */
+ * by a workgroup that processed no tile. accumulate = 3 / 4 (after the deferred-fold mode of
+ * lgnn_gcn_stack_bwd_s3f, see there; tile_open required): db as for 1 / 2, the dW slot always
+ * written (zeros by a workgroup that processed no tile). Fast path only. */
 int lgnn_node_linear_bwd_tiles(int grad_mode, const float* dY, const int64_t* batch,
                                const int32_t* gptr, int pool_mean, const int32_t* tptr,
                                const int32_t* tidx, const float* tw, float tself, const float* H,
@@ -731,6 +733,46 @@ int lgnn_gcn_stack_bwd_s3f_ce(const int64_t* batch, const int32_t* gptr, int poo
                               float* dS_ws, int32_t* tile_open, const struct lgnn_ce_src* ce,
                               const float* Wout, int num_classes, const void* adjt,
                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Deferred fold: a mode of lgnn_gcn_stack_bwd_s3f / _all / _ce for L <= 2, selected by
+ * H[0] == NULL (nothing reads H_0 then). dW_0 = W_1^T T, db_0 = W_1^T g and
+ * dW_1 = T W_0^T + g b_0^T are all linear in T = G_1^T X ([widths[2]][widths[0]]) and
+ * g = colsum G_1 ([widths[2]]), so the closed tiles form none of them: each workgroup sums T and g
+ * over its tiles and writes them into slot b of dWp[L + 1] / dbp[L + 1] — the host arrays hold
+ * L + 2 entries in this mode (and only in this mode is that position read). EVERY workgroup
+ * writes its T / g slot (zeros without a closed tile; these slabs have no skip words).
+ * dbp[L + 1] holds one more 4-byte word behind its num_partials * widths[2] floats: the launch
+ * writes the number of closed tiles there (int32). When it is 0 the T / g slabs are dead, as the
+ * open-only slabs are without an open tile: no workgroup writes them, their reductions take the
+ * word as `live`, and lgnn_gcn_fold_wgrad (its `live`) forms nothing.
+ * dWp[2..L] and dbp[1..L] with their skip words are as in the legacy mode. dWp[0], dbp[0] and
+ * dWp[1] receive the open tiles' directly formed sums only, overwriting: from the open phase of
+ * the _all / _ce launch (if the count word of tile_open is 0 they are not written at all), or
+ * after lgnn_gcn_stack_bwd_s3f from lgnn_node_linear_bwd_tiles(..., want_open = 1) with
+ * accumulate = 0 for in_proj and accumulate = 4 for the first conv (its dW slot is always
+ * written, zeros without a tile; its db as for accumulate = 2; 3 likewise with db as for 1),
+ * accumulate = 2 above it.
+ * The caller reduces the slabs — lgnn_reduce_jobs_live skips the open-only ones when no tile is
+ * open — and runs lgnn_gcn_fold_wgrad once:
+ *   dW0 = W1^T T (+ dW0_open), db0 = W1^T g (+ db0_open), dW1 = T W0^T + g b0^T (+ dW1_open)
+ * from the reduced T [w2][d_in] and g [w2], the fp32 W0 [w1][d_in], b0 [w1] and W1 [w2][w1];
+ * the *_open totals are nullable and may be the outputs themselves (added in place). live
+ * (nullable device int32): 0 = T and g count as zero and are not used (outputs = the open totals). Widths
+ * <= 128 and % 4 == 0 (else LGNN_EINVAL). FMA chains in index order, one thread per output
+ * element (fp32; db0's in double): no atomics, bitwise repeatable.
+ * lgnn_reduce_jobs_live = lgnn_reduce_jobs_ce (ce_job nullable: no CE job) + live: a host array
+ * of n nullable device int32 pointers; where *live[j] == 0 the slab of job j is not read (it may
+ * be uninitialised) and out_j is zeros. Live jobs sum in lgnn_reduce_jobs' order, bitwise.
+ * ------------------------------------------------------------------------------------------- */
+int lgnn_gcn_fold_wgrad(const float* T, const float* g, const float* W0, const float* b0,
+                        const float* W1, int d_in, int w1, int w2, const float* dW0_open,
+                        const float* db0_open, const float* dW1_open, const int32_t* live,
+                        float* dW0, float* db0, float* dW1, void* stream);
+int lgnn_reduce_jobs_live(int n, const float* const* partials, const float* const* factor,
+                          const int* width, const int* num_partials, const int64_t* len,
+                          float* const* out, const int* ce_job, const struct lgnn_ce_src* ce,
+                          int num_classes, const int32_t* const* live, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense GEMMs at fp32 accuracy on bf16 MFMA ("split-3"), any width. Replace: the plain

@@ -145,6 +145,9 @@ struct ReduceJobs {
   int64_t len[LGNN_MAX_REDUCE];
   int P[LGNN_MAX_REDUCE];
   int width[LGNN_MAX_REDUCE];
+  // nullable device word per job: 0 = the slab is dead (never written, possibly NaN): it is not
+  // read and out is zeros (lgnn_reduce_jobs_live)
+  const int32_t* live[LGNN_MAX_REDUCE];
 };
 
 constexpr int RT = 1024;
@@ -160,6 +163,18 @@ __global__ __launch_bounds__(RT) void k_reduce_multi(ReduceJobs jobs) {
   const float* __restrict__ part = jobs.part[j];
   int P = jobs.P[j];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (const int32_t* lv = jobs.live[j]; lv && *lv == 0) {  // dead slab: zeros, nothing read
+    if (wave == 0) {
+      if (vec) {
+        const int64_t i4 = (int64_t)blockIdx.x * 256 + 4 * lane;
+        if (i4 < len) st4(jobs.out[j] + i4, f32x4{0.f, 0.f, 0.f, 0.f});
+      } else {
+        const int64_t i = (int64_t)blockIdx.x * 64 + lane;
+        if (i < len) jobs.out[j][i] = 0.f;
+      }
+    }
+    return;
+  }
   if (vec) {
     const int64_t i4 = (int64_t)blockIdx.x * 256 + 4 * lane;
     const int64_t ic4 = i4 < len ? i4 : len - 4;
@@ -347,7 +362,7 @@ extern "C" int lgnn_reduce_partials_multi(int n, const float* const* partials,
 static int reduce_jobs(int n, const float* const* partials, const float* const* factor,
                        const int* width, const int* num_partials, const int64_t* len,
                        float* const* out, const int* ce_job, const lgnn_ce_src* ce, int C,
-                       void* stream) {
+                       void* stream, const int32_t* const* live = nullptr) {
   if (n <= 0 || n > LGNN_MAX_REDUCE || !partials || !num_partials || !len || !out)
     return LGNN_EINVAL;
   ReduceJobs jobs = {};
@@ -375,6 +390,7 @@ static int reduce_jobs(int n, const float* const* partials, const float* const* 
     jobs.out[j] = out[j];
     jobs.len[j] = len[j];
     jobs.P[j] = num_partials[j];
+    jobs.live[j] = live ? live[j] : nullptr;
     if (len[j] > maxlen) maxlen = len[j];
   }
   if (maxlen == 0) return LGNN_OK;
@@ -399,4 +415,14 @@ extern "C" int lgnn_reduce_jobs_ce(int n, const float* const* partials,
   if (!ce_job) return LGNN_EINVAL;
   return reduce_jobs(n, partials, factor, width, num_partials, len, out, ce_job, ce, num_classes,
                      stream);
+}
+
+extern "C" int lgnn_reduce_jobs_live(int n, const float* const* partials,
+                                     const float* const* factor, const int* width,
+                                     const int* num_partials, const int64_t* len,
+                                     float* const* out, const int* ce_job, const lgnn_ce_src* ce,
+                                     int num_classes, const int32_t* const* live, void* stream) {
+  if (!live) return LGNN_EINVAL;
+  return reduce_jobs(n, partials, factor, width, num_partials, len, out, ce_job, ce, num_classes,
+                     stream, live);
 }

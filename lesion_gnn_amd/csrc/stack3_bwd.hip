@@ -711,7 +711,17 @@ __device__ __forceinline__ void open_dz0(float* __restrict__ dZ0, const float* _
 // layers of dW fill the accumulator registers (192 of 512 per lane at one wave per SIMD), a fourth
 // would spill — the kernel writes dZ_0 (the in_proj output gradient) instead and the caller forms
 // dW_0 = dZ_0^T X, db_0 = colsum dZ_0 with one split-3 weight-gradient GEMM (lgnn_s3_wgrad)
-template <int NL, bool AG, bool XIN = false>
+//
+// DF (deferred fold, L <= 2 with in_proj; selected by H[0] == NULL): dW_0, db_0 and dW_1 are all
+// linear in T = sum G_1^T X and g = sum colsum G_1, so none of them is formed here: the first
+// conv accumulates T and g only (no H_0 rows, no H_0 image, no dW_1 accumulators), there is no
+// W_1^T T product after the tile loop, and the workgroup writes T ([w2][d_in]) and g ([w2]) into
+// slot blockIdx.x of dWp[L + 1] / dbp[L + 1] — every workgroup, zeros without a closed tile (no
+// skip words), unless the launch has no closed tile at all: the count word behind the g slab is
+// then 0 and the slabs are dead. One lgnn_gcn_fold_wgrad launch per step forms the three
+// gradients from the reduced T and g.
+// dWp[0], dbp[0] and dWp[1] receive the open tiles' direct sums only (the open phase overwrites).
+template <int NL, bool AG, bool XIN = false, bool DF = false>
 __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ rowptr,
                                                    const int32_t* __restrict__ col,
                                                    const float* __restrict__ w, int64_t M,
@@ -719,6 +729,7 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
                                                    OpenBwdArgs o) {
   constexpr int L = NL - 1;
   constexpr int ND = XIN ? NL - 1 : NL;  // layers whose dW is accumulated here
+  static_assert(!DF || (!XIN && NL <= 3), "deferred fold: in_proj folded behind the first conv");
   __shared__ __attribute__((aligned(16))) FBwdSmem sm;
   const int64_t ntiles = (M + TM - 1) / TM;
   float* const scr = reinterpret_cast<float*>(sm.Adj[0]);  // fp32 Â^T [source][target]
@@ -963,7 +974,8 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       {
         const int tq = fresh_tid();
         const int h = (tq >> 5) & 1, k = 32 * (tq >> 6) + (tq & 31);
-        load_pt(hp, a.H[l - 1], (ABL & 16) ? 0 : M, r0, K, k, K, h);
+        // (deferred fold: nothing reads H_0)
+        if (!(DF && fold)) load_pt(hp, a.H[l - 1], (ABL & 16) ? 0 : M, r0, K, k, K, h);
       }
       // db_l: this lane's 32 nodes, then the partner half's
       {
@@ -1059,7 +1071,7 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       }
       STAMP(stamp++);
       // H_{l-1} -> feature-major image (the previous layer's dW readers passed its barrier)
-      {
+      if (!(DF && fold)) {
         const int tq = fresh_tid();
         const int h = (tq >> 5) & 1, li = tq & 31, k = 32 * (tq >> 6) + li;
 #pragma unroll
@@ -1152,12 +1164,14 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
             for (int kb = 0; kb < 4; ++kb) {
               u32x4 hb[3], xb[3];
               const int off = hf_chunk(32 * kb + li, 2 * s + h);
+              if constexpr (!DF) {
 #pragma unroll
-              for (int p = 0; p < 3; ++p) hb[p] = lds16(sm.Img[p] + off);
+                for (int p = 0; p < 3; ++p) hb[p] = lds16(sm.Img[p] + off);
+              }
 #pragma unroll
               for (int p = 0; p < 3; ++p) xb[p] = lds16(sm.Gt[p] + off);
               if constexpr (!(ABL & 1)) {
-                dw[1][kb] = mfma_s3(gp[s], hb, dw[1][kb]);
+                if constexpr (!DF) dw[1][kb] = mfma_s3(gp[s], hb, dw[1][kb]);
                 dw[0][kb] = mfma_s3(gp[s], xb, dw[0][kb]);
               }
             }
@@ -1281,8 +1295,34 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
   }
   // partial slot blockIdx.x of every layer: dW rows n = 32 wave + (r & 3) + 8 (r >> 2) + 4h,
   // columns k = 32 kb + li; db from the h = 0 lanes
+  // the launch's closed-tile count, behind the g slab: the `live` word of the T / g reductions and
+  // of the fold launch. Without any closed tile the T / g slabs are dead (as the open-only slabs
+  // are without an open tile): no workgroup writes its slot and nobody reads them
+  const int closed_tiles = DF ? (int)ntiles - tmask[ntiles] : 0;
+  if (DF && blockIdx.x == 0 && threadIdx.x == 0)
+    *reinterpret_cast<int32_t*>(a.dbp[NL] + (int64_t)gridDim.x * a.width[2]) = closed_tiles;
+  if (DF && closed_tiles > 0) {
+    // T and g, slot blockIdx.x of the extra slabs: rows n = 32 wave + (r & 3) + 8 (r >> 2) + 4h
+    // of G_1's features, columns k = 32 kb + li of X's; every workgroup (zeros without a tile:
+    // these slabs have no skip words)
+    const int tq = threadIdx.x;
+    const int h = (tq >> 5) & 1, li = tq & 31, wv = tq >> 6;
+    const int N = a.width[2], K = a.width[0];
+    float* slab = a.dWp[NL] + (int64_t)blockIdx.x * N * K;
+#pragma unroll
+    for (int kb = 0; kb < 4; ++kb) {
+      const int k = 32 * kb + li;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = 32 * wv + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (n < N && k < K) st_wt(slab + (int64_t)n * K + k, dw[0][kb][r]);
+      }
+    }
+    const int n = 32 * wv + li;
+    if (h == 0 && n < N) a.dbp[NL][(int64_t)blockIdx.x * N + n] = dbacc[0];
+  }
   if (write_slots) {
-    if constexpr (!XIN) {
+    if constexpr (!XIN && !DF) {
       // in_proj's partial from the folded sums, once per workgroup: dW_0 = W_1^T T and
       // db_0 = W_1^T g, with T = sum over the tiles of G_1^T X (dw[0]: rows n of W_1, columns
       // k of X) and g = sum of colsum G_1 (dbacc[0], lane n). T goes through LDS as a
@@ -1376,11 +1416,11 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
     const int tq = threadIdx.x;
     const int h = (tq >> 5) & 1, li = tq & 31, wv = tq >> 6;
 #pragma unroll
-    for (int l = XIN ? 1 : 0; l < NL; ++l) {
+    for (int l = (XIN || DF) ? 1 : 0; l < NL; ++l) {
       const int N = a.width[l + 1], K = a.width[l];
       float* slab = a.dWp[l] + (int64_t)blockIdx.x * N * K;
 #pragma unroll
-      for (int kb = 0; kb < 4; ++kb) {
+      for (int kb = 0; kb < (DF && l == 1 ? 0 : 4); ++kb) {  // (DF: dW_1 comes from the fold)
         const int k = 32 * kb + li;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1404,22 +1444,25 @@ __global__ __launch_bounds__(NT, 1) void k_s3_fbwd(const int32_t* __restrict__ r
       if (l < L) grid_sync(o.sync, L - l);  // dS of layer l + 1 complete for every open tile
       const int K = a.width[l], N = a.width[l + 1];
       const float* Sx = l == 0 ? a.X : o.S[l - 1];
+      // deferred fold: dWp[1] (and dWp[0] / dbp[0] below) hold the open tiles' sums only, so
+      // the first conv overwrites its dW slot (accumulate = 3) and in_proj both (0)
+      const int dw1_acc = (DF && l == 1) ? 3 : 1;
       if (l == L)
         bwd_tiles<LGNN_GRAD_POOL, LGNN_ACT_ELU, true>(
             lw.A, lw.C, lw.ti, a.dP, a.batch, a.gptr, a.pool_mean, nullptr, nullptr, nullptr, 0.f,
-            a.H[l], Sx, M, K, o.W[l], N, o.dS[l & 1], a.dWp[l], a.dbp[l], tmask, 1, 1, a.dlog,
+            a.H[l], Sx, M, K, o.W[l], N, o.dS[l & 1], a.dWp[l], a.dbp[l], tmask, 1, dw1_acc, a.dlog,
             a.Wout, a.C, BnFuse{}, a.ce);
       else if (l >= 1)
         bwd_tiles<LGNN_GRAD_TRANSPOSE, LGNN_ACT_ELU, true>(
             lw.A, lw.C, lw.ti, o.dS[(l + 1) & 1], a.batch, a.gptr, a.pool_mean, o.tptr, o.tidx,
             o.tw, 0.f, a.H[l], Sx, M, K, o.W[l], N, o.dS[l & 1], a.dWp[l], a.dbp[l], tmask, 1,
-            1);
+            dw1_acc);
       else if constexpr (XIN)
         open_dz0(a.dZ0, o.dS[1], o.tptr, o.tidx, o.tw, M, N, tmask);
       else
         bwd_tiles<LGNN_GRAD_TRANSPOSE, LGNN_ACT_NONE, false>(
             lw.A, lw.C, lw.ti, o.dS[1], a.batch, a.gptr, a.pool_mean, o.tptr, o.tidx, o.tw, 0.f,
-            nullptr, Sx, M, K, o.W[0], N, nullptr, a.dWp[0], a.dbp[0], tmask, 1, 1);
+            nullptr, Sx, M, K, o.W[0], N, nullptr, a.dWp[0], a.dbp[0], tmask, 1, DF ? 0 : 1);
     }
     grid_exit(o.sync);
   }
@@ -1541,12 +1584,23 @@ static int stack_bwd_s3f(const float* dP, const int64_t* batch, const int32_t* g
   a.WpT = planes_t;
   a.dZ0 = dz0;
   for (int l = 0; l <= L + 1; ++l) a.width[l] = widths[l];
+  // deferred fold (L <= 2): H[0] == NULL, and dWp / dbp hold one more entry, the T / g slabs.
+  // A NULL H[0] used to be refused: a caller that passes it selects this mode, and its host
+  // arrays are then read at [L + 1] (include/lgnn.h states the contract; nothing here can check
+  // the arrays' length)
+  const bool defer = L <= 2 && !H[0];
   for (int l = 0; l <= L; ++l) {
-    if (!lgnn_tile_fits(M, widths[l], widths[l + 1]) || !H[l] || !dWp[l] || !dbp[l])
+    if (!lgnn_tile_fits(M, widths[l], widths[l + 1]) || (!H[l] && !(defer && l == 0)) ||
+        !dWp[l] || !dbp[l])
       return LGNN_EINVAL;
     a.H[l] = H[l];
     a.dWp[l] = dWp[l];
     a.dbp[l] = dbp[l];
+  }
+  if (defer) {
+    if (!dWp[L + 1] || !dbp[L + 1]) return LGNN_EINVAL;
+    a.dWp[L + 1] = dWp[L + 1];
+    a.dbp[L + 1] = dbp[L + 1];
   }
   hipStream_t s = as_stream(stream);
   if (M == 0) {
@@ -1554,6 +1608,11 @@ static int stack_bwd_s3f(const float* dP, const int64_t* batch, const int32_t* g
       if (hipMemsetAsync(dWp[l], 0, (size_t)widths[l] * widths[l + 1] * 4, s) != hipSuccess ||
           hipMemsetAsync(dbp[l], 0, (size_t)widths[l + 1] * 4, s) != hipSuccess)
         return (int)hipGetLastError();
+    if (defer && (hipMemsetAsync(dWp[L + 1], 0, (size_t)widths[2] * widths[0] * 4, s) != hipSuccess ||
+                  hipMemsetAsync(dbp[L + 1], 0, (size_t)widths[2] * 4, s) != hipSuccess ||
+                  hipMemsetAsync(dbp[L + 1] + (size_t)num_partials * widths[2], 0, 4, s) !=
+                      hipSuccess))  // the closed-tile count word
+      return (int)hipGetLastError();
     return LGNN_OK;
   }
   const dim3 grid((unsigned)num_partials), blk(lgnn_tile::NT);
@@ -1567,6 +1626,18 @@ static int stack_bwd_s3f(const float* dP, const int64_t* batch, const int32_t* g
   else if (L == 3)
     hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<4, false, true>), grid, blk, 0, s, rowptr, col, w, M,
                        a, tile_open, o);
+  else if (defer && L == 1 && adjt)
+    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, true, false, true>), grid, blk, 0, s, rowptr, col,
+                       w, M, a, tile_open, o);
+  else if (defer && L == 1)
+    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, false, false, true>), grid, blk, 0, s, rowptr, col,
+                       w, M, a, tile_open, o);
+  else if (defer && adjt)
+    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, true, false, true>), grid, blk, 0, s, rowptr, col,
+                       w, M, a, tile_open, o);
+  else if (defer)
+    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, false, false, true>), grid, blk, 0, s, rowptr, col,
+                       w, M, a, tile_open, o);
   else if (L == 1 && adjt)
     hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, true>), grid, blk, 0, s, rowptr, col, w, M, a,
                        tile_open, o);

@@ -532,11 +532,16 @@ __device__ __forceinline__ void bwd_tiles(
   // accumulate: add into slot blockIdx.x (written by the fused stack backward) if this
   // workgroup processed any tile; otherwise leave the slot untouched. accumulate = 2: a slot
   // whose skip word is set was not written by the fused kernel: write it (zeros when this
-  // workgroup processed no tile)
-  const bool skipped = accumulate == 2 && blockIdx.x < LGNN_SLOT_FLAGS &&
+  // workgroup processed no tile). accumulate = 3 / 4: db as for 1 / 2, but the dW slot holds
+  // nothing yet (the fused kernel's deferred fold wrote no dW for this layer): always written,
+  // with zeros by a workgroup that processed no tile
+  const bool dw_over = accumulate >= 3;
+  const int acc = dw_over ? accumulate - 2 : accumulate;
+  const bool skipped = acc == 2 && blockIdx.x < LGNN_SLOT_FLAGS &&
                        tmask[ntiles + LGNN_SLOT_FLAG0 + blockIdx.x] != 0;
-  if (accumulate && tfirst >= ntiles && !skipped) return;
-  const bool add = accumulate && !skipped;
+  const bool leave = acc && tfirst >= ntiles && !skipped;  // the slot stays as it is
+  if (leave && !dw_over) return;
+  const bool add = acc && !skipped;
   float* slab = dWp + (int64_t)blockIdx.x * N * K;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -546,11 +551,11 @@ __device__ __forceinline__ void bwd_tiles(
       const int o = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
       if (o < N && k < K) {
         float* p = slab + (int64_t)o * K + k;
-        *p = add ? *p + dw[j][r] : dw[j][r];
+        *p = (add && !dw_over) ? *p + dw[j][r] : dw[j][r];
       }
     }
   }
-  if (dbp && tid < N) {
+  if (dbp && tid < N && !leave) {
     float* p = dbp + (int64_t)blockIdx.x * N + tid;
     *p = add ? *p + dbacc : dbacc;
   }

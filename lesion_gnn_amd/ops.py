@@ -127,6 +127,11 @@ OPEN_IN_FUSED_BWD = OPEN_IN_FUSED
 # dP = dlogits W_out formed inside the single-launch split-3 backward (HEAD_FOLD = False: by
 # lgnn_pool_head_bwd before it)
 HEAD_FOLD = True
+# the fused split-3 backward (L <= 2) defers the in_proj fold: its closed tiles only sum
+# T = G_1^T X and g = colsum G_1 (no H_0 read, no dW_1 products, no W_1^T T per workgroup) and one
+# lgnn_gcn_fold_wgrad launch per step forms dW_0, db_0 and dW_1 from the reduced sums
+# (DEFER_FOLD = False: the kernel's legacy mode, every gradient per workgroup)
+DEFER_FOLD = True
 _CAPACITY: dict = {}
 
 
@@ -334,13 +339,20 @@ def head_in_stack_bwd(graph: Graph, L: int, C: int, s3: bool) -> bool:
 
 def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool, Ws: list,
               hs: list, ss: list, reducer: list, planes_t: torch.Tensor | None = None,
-              head: tuple | None = None, kind: str = "gcn", adjt_t: torch.Tensor | None = None):
+              head: tuple | None = None, kind: str = "gcn", adjt_t: torch.Tensor | None = None,
+              b0: torch.Tensor | None = None):
     """Backward of stack_fwd from the pooled-output gradient dp down to in_proj, L >= 1 convs,
     no input gradient. Closed tiles run fused (one launch; L = 3 with in_proj's weight gradient
     as a split-3 GEMM after it, the layer-major split-3 kernels past that); open tiles inside the
     same launch behind grid barriers, or layer by layer (lgnn_node_linear_bwd_tiles,
-    want_open = 1) into the same partial slots. Returns [(dW_l, db_l)] for l = 0..L; the slab reductions are appended
-    to `reducer`. head = (dlogits, W_out) replaces dp where head_in_stack_bwd() allows."""
+    want_open = 1) into the same partial slots. Returns ([(dW_l, db_l)] for l = 0..L, after): the
+    slab reductions are appended to `reducer`, and `after` (None, or the deferred fold's launch) is
+    for the caller to run once they are launched. head = (dlogits, W_out) replaces dp where
+    head_in_stack_bwd() allows.
+    b0 (in_proj's bias; with DEFER_FOLD, s3f and L <= 2): the kernel's deferred mode — H_0 is not
+    passed, the slabs gain the T / g pair, layers 0 and 1 keep open-tile-only slabs whose
+    reductions carry the open-tile count as their `live` word, and the fold launch is returned
+    for the caller to run behind the reductions."""
     csr = graph.csr(kind)
     open_ = graph.tile_open(kind)
     M = x.size(0)
@@ -357,10 +369,16 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
     _lib.check(0 if P > 0 else P, "lgnn_gcn_stack_bwd_partials")
     widths = [x.size(1)] + [W.size(0) for W in Ws]
     per = [widths[l + 1] * widths[l] + widths[l + 1] for l in range(L + 1)]
-    slab = torch.empty(P * sum(per), dtype=torch.float32, device=dev)
+    defer = DEFER_FOLD and s3f and L <= 2 and b0 is not None
+    if defer:  # the T [w2][d_in] / g [w2] slabs ride behind the layers'
+        per.append(widths[2] * widths[0] + widths[2])
+        hs = [None] + list(hs[1:])
+    # (defer: one more word behind the g slab, the launch's closed-tile count)
+    slab = torch.empty(P * sum(per) + int(defer), dtype=torch.float32, device=dev)
     dWp, dbp, off = [], [], 0
-    for l in range(L + 1):
-        nk, n = widths[l + 1] * widths[l], widths[l + 1]
+    for l in range(L + 2 if defer else L + 1):
+        nk, n = (widths[2] * widths[0], widths[2]) if l == L + 1 else \
+            (widths[l + 1] * widths[l], widths[l + 1])
         dWp.append(slab[off:off + P * nk])
         dbp.append(slab[off + P * nk:off + P * (nk + n)])
         off += P * (nk + n)
@@ -383,8 +401,11 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
         if L == 3:  # in_proj: (dW_0, db_0) = (dZ_0^T X, colsum dZ_0), one split-3 GEMM
             dz0 = dS_ws[2 * M * 128:2 * M * 128 + M * widths[1]].view(M, widths[1])
             first = dense_wgrad(dz0, x, False, want_db=True, reducer=reducer)
-            return [first] + _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer, l0=1)
-        return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer)
+            return [first] + _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer, l0=1), None
+        if defer:
+            return _stack_bwd_outputs_defer(L, widths, dWp, dbp, P, dev, reducer, Ws, b0, open_,
+                                            M, slab)
+        return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer), None
     assert head is None, "dP from the logits gradient only in the single-launch split-3 path"
     if s3f:  # one fused split-3 launch, every layer of a tile in one pass (stack3_bwd.hip)
         _lib.call("lgnn_gcn_stack_bwd_s3f", dp, graph.batch, graph.gptr, int(mean), dp.size(0),
@@ -409,10 +430,42 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
         _lib.call("lgnn_node_linear_bwd_tiles", mode, dY, graph.batch, graph.gptr, int(mean),
                   tc.tptr, tc.tidx, tc.tw, 0.0, hs[l] if l > 0 else None,
                   _lib.LGNN_ACT_ELU if l > 0 else _lib.LGNN_ACT_NONE, Sx[l], M, K, None, None,
-                  None, 0.0, Ws[l], N, dX, dWp[l], dbp[l], P, open_, 1, 2 if s3f else 1,
-                  _s(dev))
+                  None, 0.0, Ws[l], N, dX, dWp[l], dbp[l], P, open_, 1,
+                  ((0, 4)[l] if l < 2 else 2) if defer else 2 if s3f else 1, _s(dev))
         dS = dX
-    return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer)
+    if defer:
+        return _stack_bwd_outputs_defer(L, widths, dWp, dbp, P, dev, reducer, Ws, b0, open_, M,
+                                        slab)
+    return _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer), None
+
+
+def _stack_bwd_outputs_defer(L, widths, dWp, dbp, P, dev, reducer, Ws, b0, open_, M, slab):
+    """(_stack_bwd_outputs for the deferred fold, the fold launch as a callable). dW_0, db_0 and
+    dW_1 first receive the open tiles' totals (slabs that are dead when the open-tile count word
+    is 0: `live`); the fold launch, which the caller runs after the reductions, adds W_1^T T,
+    W_1^T g and T W_0^T + g b_0^T. The T / g slabs are dead when the launch's closed-tile count
+    (the last word of `slab`) is 0."""
+    d_in, w1, w2 = widths[0], widths[1], widths[2]
+    live = open_[(M + 63) // 64:]  # the open-tile count word
+    closed = slab[-1:].view(torch.int32)  # the closed-tile count word
+    T = torch.empty(w2, d_in, dtype=torch.float32, device=dev)
+    g = torch.empty(w2, dtype=torch.float32, device=dev)
+    out = []
+    for l in range(L + 1):
+        dW = torch.empty(widths[l + 1], widths[l], dtype=torch.float32, device=dev)
+        db = torch.empty(widths[l + 1], dtype=torch.float32, device=dev)
+        reducer.extend([(dWp[l], P, dW.numel(), dW, None, 0, live if l < 2 else None),
+                        (dbp[l], P, db.numel(), db, None, 0, live if l < 1 else None)])
+        out.append((dW, db))
+    reducer.extend([(dWp[L + 1], P, T.numel(), T, None, 0, closed),
+                    (dbp[L + 1], P, g.numel(), g, None, 0, closed)])
+    (dW0, db0), dW1 = out[0], out[1][0]
+
+    def fold():  # the open totals are added in place (element by element: aliasing is safe)
+        _lib.call("lgnn_gcn_fold_wgrad", T, g, Ws[0], b0, Ws[1], d_in, w1, w2, dW0, db0, dW1,
+                  closed, dW0, db0, dW1, _s(dev))
+
+    return out, fold
 
 
 def _stack_bwd_outputs(L, widths, dWp, dbp, P, dev, reducer, l0=0):
@@ -488,7 +541,8 @@ def reduce_multi(jobs: list, dev, ce=None, num_classes: int = 0) -> None:
     """Deterministic slab reductions [(partials, P, len, out), ...] in one launch per 16; a job
     (a, P, len, out, f, width) is the outer-product sum out[c, d] = sum_p a[p, c] f[p, d]. A job
     whose partials are CE_PART takes the [P][C] CE logits gradient formed from `ce`
-    (_lib.CeSrc, lgnn_reduce_jobs_ce) instead of a materialised dlogits tensor."""
+    (_lib.CeSrc, lgnn_reduce_jobs_ce) instead of a materialised dlogits tensor. A seventh field is
+    the job's `live` word (a device int32, lgnn_reduce_jobs_live: 0 = slab not read, out zeros)."""
     for i in range(0, len(jobs), 16):
         chunk = jobs[i:i + 16]
         n = len(chunk)
@@ -499,7 +553,15 @@ def reduce_multi(jobs: list, dev, ce=None, num_classes: int = 0) -> None:
         outs = [j[3] for j in chunk]
         fac = [j[4] if len(j) > 4 else None for j in chunk]
         wid = [j[5] if len(j) > 4 else 0 for j in chunk]
-        if any(is_ce):
+        live = [j[6] if len(j) > 6 else None for j in chunk]
+        if any(lv is not None for lv in live):
+            if any(is_ce) and ce is None:
+                raise _lib.LgnnError("reduce_multi: a CE_PART job needs the CE source")
+            _lib.call("lgnn_reduce_jobs_live", n, parts, fac, wid, nps, lens, outs,
+                      [int(c) for c in is_ce] if any(is_ce) else None,
+                      ctypes.byref(ce) if any(is_ce) else None, int(num_classes), live,
+                      _s(dev))
+        elif any(is_ce):
             if ce is None:
                 raise _lib.LgnnError("reduce_multi: a CE_PART job needs the CE source")
             _lib.call("lgnn_reduce_jobs_ce", n, parts, fac, wid, nps, lens, outs,
@@ -1141,18 +1203,20 @@ def gcn_stack_bwd(sv: GcnSaved, dlogits, want_dx: bool, ce=None):
             dbo = torch.empty(C, dtype=torch.float32, device=x.device)
             part = CE_PART if ce is not None else dlogits
             red += [(part, B, C * D, dWo, pooled, D), (part, B, C, dbo)]
-            outs = stack_bwd(None, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t,
-                             head=(ce[0] if ce is not None else dlogits, W_out), kind=kind,
-                             adjt_t=sv.adjt)
+            outs, after = stack_bwd(None, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t,
+                                    head=(ce[0] if ce is not None else dlogits, W_out),
+                                    kind=kind, adjt_t=sv.adjt, b0=params[1])
         else:
             dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
-            outs = stack_bwd(dp, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t, kind=kind,
-                             adjt_t=sv.adjt)
+            outs, after = stack_bwd(dp, x, graph, sv.mean, Ws, hs, ss, red, sv.planes_t,
+                                    kind=kind, adjt_t=sv.adjt, b0=params[1])
         grads[2 + 2 * L], grads[3 + 2 * L] = dWo, dbo
         for l, (dW, db) in enumerate(outs):
             grads[2 * l], grads[2 * l + 1] = dW, db
         reduce_multi(red, x.device, ce=ce[0] if ce is not None else None,
                      num_classes=W_out.size(0))
+        if after is not None:  # the deferred fold, on the reduced sums
+            after()
         return None, grads
     assert ce is None, "the CE-formed logits gradient only on the fused head path"
     dp, dWo, dbo = pool_head_bwd(dlogits, pooled, W_out)
