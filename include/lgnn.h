@@ -1233,6 +1233,39 @@ int lgnn_bn_bwd_apply_a(const float* dA, const float* Z, const float* mask, int6
                         const float* invstd, int act, const double* sums, double count,
                         int training, float* dZ, float* dgamma, float* dbeta, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Collation of a batch out of a device-resident graph dataset. Replaces: the per-step work of
+ * torch_geometric.loader.DataLoader's Collater / Batch.from_data_list over the InMemoryDataset
+ * (reference src/lesion_gnn/datasets/datamodule.py:63-69, datasets/base.py:27-115) for the
+ * attributes x, pos, y, batch and ptr. The entries are additions: every earlier signature is
+ * unchanged, so the ABI version stays.
+ *   The dataset: x [rows, channels] fp32, pos [rows, dims] fp64 (dims 2 or 3; NULL: no positions,
+ *   out_pos is not written), y [num_src_graphs] int64, src_ptr [num_src_graphs + 1] int64 (graph
+ *   g owns rows [src_ptr[g], src_ptr[g + 1])). ids [num_sel] int64: the graphs of the batch, in
+ *   batch order; repeats are legal.
+ *   With n_b = src_ptr[ids[b] + 1] - src_ptr[ids[b]]: out_ptr [num_sel + 1] = the exclusive scan
+ *   of n_b; out_batch[r] = b and out_x[out_ptr[b] + t] = x[src_ptr[ids[b]] + t] (out_pos
+ *   likewise) for r = out_ptr[b] + t, t < n_b; out_y[b] = y[ids[b]].
+ *   out_capacity: the rows out_x / out_pos / out_batch hold. The row total is read on the device
+ *   (every device-side size is, so a captured call replays on refilled ids): rows at or beyond it
+ *   are left untouched, and nothing is written at or beyond row out_capacity.
+ *   err [1] int32, written: the number of ids outside [0, num_src_graphs) (each counts as an
+ *   empty graph, out_y = -1), plus LGNN_COLLATE_OVERFLOW when the total exceeds out_capacity
+ *   (out_ptr and out_y are complete all the same).
+ *   out_x must be 16-byte aligned (all its stores are 16-byte stores); x, and the row width
+ *   channels * 4, need not be. workspace: lgnn_collate_workspace_bytes(num_sel). num_sel = 0
+ *   writes out_ptr[0] = 0 and err. Three launches (the gather is skipped when num_sel or
+ *   out_capacity is 0), no host synchronisation. LGNN_EINVAL, before any launch: a negative count, channels < 1, dims not in
+ *   {0, 2, 3}, a NULL required pointer, a workspace that is too small.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_COLLATE_OVERFLOW 1073741824
+size_t lgnn_collate_workspace_bytes(int64_t num_sel);
+int lgnn_collate(const int64_t* ids, int64_t num_sel, const int64_t* src_ptr,
+                 int64_t num_src_graphs, const float* x, int channels, const double* pos,
+                 int dims, const int64_t* y, float* out_x, double* out_pos, int64_t* out_y,
+                 int64_t* out_batch, int64_t* out_ptr, int64_t out_capacity, int32_t* err,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

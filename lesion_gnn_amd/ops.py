@@ -13,6 +13,7 @@
 - `edge_sub`        PointNetConv's split first Linear over the pairs of a cluster.PairGraph;
                     `bn_act_rows` (BatchNorm + ReLU / ELU [+ dropout mask] over rows),
                     `segment_max` (the max aggregation and global_max_pool)
+- `collate`         a selection of graphs of a device-resident datasets.GraphStore as one batch
 """
 from __future__ import annotations
 
@@ -2306,6 +2307,51 @@ def ccl_stats(labels: torch.Tensor, num_labels: int,
     if validate and int(err.item()):
         raise IndexError(f"ccl_stats: {int(err.item())} labels outside [0, {n})")
     return stats, centroids
+
+
+def collate(store, ids, validate: bool = False):
+    """The graphs `ids` (host int64 tensor or list; repeats allowed) of a datasets.GraphStore as
+    one synth.Batch on the store's device (lgnn_collate): x, pos, y, batch, ptr as PyG's Collater
+    gives them, an empty [2, 0] edge_index and num_graphs set. An id outside [0, len(store))
+    raises IndexError before any launch. The output is sized from the store's host copy of ptr:
+    nothing is read back from the device, unless validate, which reads err and raises if the
+    kernel skipped an id or ran out of rows."""
+    from .synth import Batch
+
+    ids = torch.as_tensor(ids, dtype=torch.int64, device="cpu").reshape(-1)
+    G, B = len(store), ids.numel()
+    if B and (int(ids.min()) < 0 or int(ids.max()) >= G):
+        raise IndexError(f"collate: graph ids must be in [0, {G})")
+    _lib.require_gpu(store.x, store.pos, store.y, store.ptr)
+    dev = store.x.device
+    sizes = store.ptr_host[ids + 1] - store.ptr_host[ids]
+    total = int(sizes.sum())
+    C = store.x.size(1)
+    # a tensor without elements has no address: the buffers hold one row at least
+    x = store.x if store.x.size(0) else torch.zeros(1, C, dtype=torch.float32, device=dev)
+    out_x = torch.empty(max(total, 1), C, dtype=torch.float32, device=dev)
+    out_batch = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+    pos, out_pos, dims = store.pos, None, 0
+    if pos is not None:
+        dims = pos.size(1)
+        out_pos = torch.empty(max(total, 1), dims, dtype=torch.float64, device=dev)
+        if not pos.size(0):
+            pos = torch.zeros(1, dims, dtype=torch.float64, device=dev)
+    out_y = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
+    out_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    nws = _lib.load().lgnn_collate_workspace_bytes(B)
+    ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+    ids_dev = ids.to(dev)
+    _lib.call("lgnn_collate", ids_dev if B else None, B, store.ptr, G, x, C, pos, dims,
+              store.y if G else out_y, out_x, out_pos, out_y, out_batch, out_ptr, total, err, ws,
+              nws, _s(dev))
+    if validate and int(err.item()):
+        raise IndexError(f"collate: err = {int(err.item())} (ids the kernel skipped, plus "
+                         f"{_lib.LGNN_COLLATE_OVERFLOW} if the rows overflowed)")
+    return Batch(out_x[:total], torch.empty(2, 0, dtype=torch.int64, device=dev),
+                 out_batch[:total], out_ptr, out_y[:B],
+                 None if out_pos is None else out_pos[:total], B)
 
 
 # ----------------------------------------------------------------------------------------------
