@@ -919,6 +919,60 @@ int lgnn_ccl_stats(const int64_t* labels, int height, int width, int num_labels,
                    double* centroids, int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lesion nodes for a batch of images of one size: the chain above and the feature pooling for
+ * every image of a batch (reference lesions.py:147-176 per image; the reference takes one image
+ * per call), with launch counts that do not depend on the batch size. Additions to the ABI: the
+ * one-image entries above are unchanged. batch * height * width < 2^31 in all of them.
+ * lgnn_label_pool_batch: logits [batch, classes, in_height, in_width] -> out [batch, height,
+ *   width] uint8; per image exactly lgnn_label_pool. One launch.
+ * lgnn_ccl_batch: image [batch, height, width] uint8 -> labels [batch * height * width] int64,
+ *   per image exactly what lgnn_ccl gives for it alone: 0 the background, components 1, 2, ...
+ *   in raster order of their first pixel, restarting in every image; no component joins two
+ *   images. num_labels [batch] int32 (components + 1 per image) and node_ptr [batch + 1] int64,
+ *   the exclusive scan of num_labels, on the device. Workspace:
+ *   lgnn_ccl_batch_workspace_bytes (0 for sizes the entry refuses). Six launches.
+ * lgnn_ccl_stats_batch: labels as above, node_ptr [batch + 1] on the device, total_nodes =
+ *   node_ptr[batch] (the caller's copy) -> stats [total_nodes, 5] int32 and centroids
+ *   [total_nodes, 2] fp64 as lgnn_ccl_stats gives them, row node_ptr[b] + l for label l of image
+ *   b, in the image's own coordinates. Labels outside [0, node_ptr[b + 1] - node_ptr[b]) are
+ *   skipped and counted in *err (written); an image whose node_ptr words leave [0, total_nodes]
+ *   has every label counted there. Three launches.
+ * lgnn_cc_pool_resample: features [batch, channels, src_height, src_width] fp32, labels [batch,
+ *   height, width] int64, node_ptr as above -> out [total_nodes, channels] fp32: row
+ *   node_ptr[b] + l is the mean (sum / max(count, 1)) or max (0 for an empty label) over the
+ *   pixels of label l of image b of the source map sampled bilinearly at (height, width),
+ *   align_corners = False as torch.nn.functional.interpolate: src = (src_height / height) *
+ *   (i + 0.5) - 0.5 clamped at 0 (formed in double, once per row and column), taps floor(src)
+ *   and the next row (clamped at the border) with the fp32 weights 1 - lambda and lambda,
+ *   columns likewise, value = wy0 * (wx0 * v00 + wx1 * v01) + wy1 * (wx0 * v10 + wx1 * v11) in
+ *   fp32. The sampled map is never stored. With (height, width)
+ *   == (src_height, src_width) the value is the source's, bit for bit, read in place. Otherwise
+ *   one source map is staged in LDS: src_height * src_width * 4 <=
+ *   LGNN_CC_POOL_RESAMPLE_MAX_SOURCE_BYTES (128 x 128), else LGNN_EINVAL. max_nodes: an upper
+ *   bound of the labels per image, 1 <= max_nodes <= LGNN_CC_POOL_MAX_SEGMENTS; it sizes the LDS
+ *   bins (the smaller, the more workgroups a CU holds), and labels at or above it are skipped
+ *   and counted in *err like those outside the image's range. counts_out [total_nodes] int32
+ *   (nullable): pixels per label. No float atomics: two calls give the same bits. Workspace:
+ *   lgnn_cc_pool_resample_workspace_bytes. Two launches + two memsets.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_CC_POOL_RESAMPLE_MAX_SOURCE_BYTES 65536
+int lgnn_label_pool_batch(const float* logits, int batch, int classes, int in_height,
+                          int in_width, uint8_t* out, int height, int width, void* stream);
+size_t lgnn_ccl_batch_workspace_bytes(int batch, int height, int width);
+int lgnn_ccl_batch(const uint8_t* image, int batch, int height, int width, int connectivity,
+                   int64_t* labels, int32_t* num_labels, int64_t* node_ptr, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int lgnn_ccl_stats_batch(const int64_t* labels, int batch, int height, int width,
+                         const int64_t* node_ptr, int total_nodes, int32_t* stats,
+                         double* centroids, int32_t* err, void* stream);
+size_t lgnn_cc_pool_resample_workspace_bytes(int batch, int height, int width, int total_nodes);
+int lgnn_cc_pool_resample(const float* features, int batch, int channels, int src_height,
+                          int src_width, const int64_t* labels, int height, int width,
+                          const int64_t* node_ptr, int total_nodes, int max_nodes, int reduce_max,
+                          float* out, int32_t* counts_out, int32_t* err, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * bf16 dense GEMMs (bf16 GEMM operands rounded round-to-nearest-even as torch's
  * .to(torch.bfloat16), fp32 accumulation and output). Replace the bf16 nn.Linear / GATConv.lin
  * GEMMs of the bf16 configuration — in_proj (reference src/lesion_gnn/models/gat.py:29,

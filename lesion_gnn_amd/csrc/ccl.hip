@@ -27,10 +27,14 @@
 // workgroup's LDS bins (labels below 1024: the background, which holds most pixels of a lesion
 // map, is label 0) or, above, to global memory; the touched bins leave as one global integer
 // atomic each. Integer sums: any order gives the same bits.
+// Every kernel carries an image dimension (ccl.h; the batch entries are in ccl_batch.hip): B
+// images of one size are labelled as one image of B * H rows in which the merge links nothing
+// across a multiple of H; roots are counted and ranked in per-image blocks, so the numbering
+// restarts with each image and the scan's offsets at the images' first blocks are node_ptr.
 #include <algorithm>
 #include <climits>
 
-#include "common.h"
+#include "ccl.h"
 
 namespace lgnn_cclk {
 
@@ -43,14 +47,16 @@ constexpr int kBins = 1024;     // labels with LDS bins (stats)
 constexpr int kRun = 8;         // consecutive pixels per lane (stats)
 
 __global__ void __launch_bounds__(kThreads)
-    k_label_pool(const float* __restrict__ logits, int K, int Hin, int Win,
+    k_label_pool(const float* __restrict__ logits, int B, int K, int Hin, int Win,
                  uint8_t* __restrict__ out, int H, int W) {
-  const int64_t o = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (o >= (int64_t)H * W) return;
+  const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (g >= (int64_t)B * H * W) return;
+  const int64_t b = g / ((int64_t)H * W), o = g - b * H * W;
   const int oy = (int)(o / W), ox = (int)(o - (int64_t)oy * W);
   const int y0 = (int)((int64_t)oy * Hin / H), y1 = (int)(((int64_t)(oy + 1) * Hin + H - 1) / H);
   const int x0 = (int)((int64_t)ox * Win / W), x1 = (int)(((int64_t)(ox + 1) * Win + W - 1) / W);
   const int64_t plane = (int64_t)Hin * Win;
+  logits += b * K * plane;
   int best = 0;
   for (int y = y0; y < y1; ++y)
     for (int x = x0; x < x1; ++x) {
@@ -66,7 +72,7 @@ __global__ void __launch_bounds__(kThreads)
       }
       best = max(best, a);
     }
-  out[o] = (uint8_t)best;
+  out[g] = (uint8_t)best;
 }
 
 __device__ __forceinline__ int32_t ld_agent(const int32_t* p) {
@@ -144,9 +150,10 @@ __global__ void __launch_bounds__(kThreads)
 
 template <bool k8>
 __global__ void __launch_bounds__(kThreads)
-    k_ccl_merge(const uint8_t* __restrict__ img, int H, int W, int nseg, int32_t* parent) {
+    k_ccl_merge(const uint8_t* __restrict__ img, int rows, int H, int W, int nseg,
+                int32_t* parent) {
   int y, x0;
-  if (!seg_task(H, nseg, y, x0)) return;
+  if (!seg_task(rows, nseg, y, x0)) return;
   const int lane = threadIdx.x & 63, x = x0 + lane;
   const bool fg = x < W && img[(int64_t)y * W + x] != 0;
   const unsigned long long mask = __ballot(fg);
@@ -159,7 +166,7 @@ __global__ void __launch_bounds__(kThreads)
     left = x > 0 && img[(int64_t)p - 1] != 0;
     if (left) unite(parent, p, p - 1);  // the run continues across the segment border
   }
-  if (y == 0) return;
+  if (y % H == 0) return;  // the first row of an image: nothing above it belongs to it
   const uint8_t* up = img + (int64_t)(y - 1) * W;
   const bool n = up[x] != 0;
   // By induction along a row's run, a pixel ends up linked to every foreground pixel among its
@@ -193,13 +200,15 @@ __device__ __forceinline__ int block_sum(int v, int32_t* wsum) {
 }
 
 __global__ void __launch_bounds__(kThreads)
-    k_ccl_compress(int32_t* parent, int64_t npix, int32_t* __restrict__ blockcount) {
+    k_ccl_compress(int32_t* parent, int64_t hw, int nbi, int32_t* __restrict__ blockcount) {
   __shared__ int32_t wsum[kWaves];
-  const int64_t base = (int64_t)blockIdx.x * kScanPix + threadIdx.x * 4;
+  // nbi blocks per image: no block holds roots of two images
+  const int b = blockIdx.x / nbi;
+  const int64_t local = (int64_t)(blockIdx.x - b * nbi) * kScanPix + threadIdx.x * 4;
   int c = 0;
   for (int j = 0; j < 4; ++j) {
-    const int64_t p = base + j;
-    if (p >= npix) break;
+    if (local + j >= hw) break;
+    const int64_t p = b * hw + local + j;
     const int32_t q = ld_agent(parent + p);
     if (q < 0) continue;
     const int32_t r = find_root(parent, q);
@@ -213,7 +222,8 @@ __global__ void __launch_bounds__(kThreads)
 }
 
 __global__ void __launch_bounds__(kScanThreads)
-    k_ccl_scan(int32_t* __restrict__ blockcount, int nb, int32_t* __restrict__ num_labels) {
+    k_ccl_scan(int32_t* blockcount, int nb, int nbi, int B, int32_t* __restrict__ num_labels,
+               int64_t* __restrict__ node_ptr) {
   __shared__ int32_t wsum[kScanThreads / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int carry = 0;
@@ -236,20 +246,30 @@ __global__ void __launch_bounds__(kScanThreads)
     carry += total;
     __syncthreads();
   }
-  if (threadIdx.x == 0) *num_labels = carry + 1;
+  // per image: its roots are the difference of the offsets of its first block and the next
+  // image's (the loop ended on a barrier, so every thread's offsets are written)
+  for (int b = threadIdx.x; b < B; b += kScanThreads) {
+    const int first = blockcount[b * nbi];
+    const int next = b + 1 < B ? blockcount[(b + 1) * nbi] : carry;
+    num_labels[b] = next - first + 1;
+    if (node_ptr) node_ptr[b] = (int64_t)first + b;
+  }
+  if (threadIdx.x == 0 && node_ptr) node_ptr[B] = (int64_t)carry + B;
 }
 
 __global__ void __launch_bounds__(kThreads)
-    k_ccl_rank(const int32_t* __restrict__ parent, int64_t npix,
+    k_ccl_rank(const int32_t* __restrict__ parent, int64_t hw, int nbi,
                const int32_t* __restrict__ blockoff, int32_t* __restrict__ rootlabel) {
   __shared__ int32_t wsum[kWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t base = (int64_t)blockIdx.x * kScanPix + threadIdx.x * 4;
+  const int b = blockIdx.x / nbi;
+  const int64_t local = (int64_t)(blockIdx.x - b * nbi) * kScanPix + threadIdx.x * 4;
+  const int64_t base = b * hw + local;
   bool root[4];
   int c = 0;
   for (int j = 0; j < 4; ++j) {
     const int64_t p = base + j;
-    root[j] = p < npix && parent[p] == (int32_t)p;
+    root[j] = local + j < hw && parent[p] == (int32_t)p;
     c += root[j];
   }
   int s = c;
@@ -259,7 +279,7 @@ __global__ void __launch_bounds__(kThreads)
   }
   if (lane == 63) wsum[wave] = s;
   __syncthreads();
-  int r = blockoff[blockIdx.x] + s - c + 1;
+  int r = blockoff[blockIdx.x] - blockoff[b * nbi] + s - c + 1;  // the rank restarts per image
   for (int w = 0; w < wave; ++w) r += wsum[w];
   for (int j = 0; j < 4; ++j)
     if (root[j]) rootlabel[base + j] = r++;
@@ -294,10 +314,21 @@ __global__ void __launch_bounds__(kThreads)
 
 __global__ void __launch_bounds__(kThreads)
     k_stats_acc(const int64_t* __restrict__ labels, int64_t npix, int W, int n, int chunks,
-                int32_t* __restrict__ stats, unsigned long long* __restrict__ sums,
-                int32_t* __restrict__ err) {
+                int gpi, const int64_t* __restrict__ node_ptr, int32_t* __restrict__ stats,
+                unsigned long long* __restrict__ sums, int32_t* __restrict__ err) {
   __shared__ int32_t b_minx[kBins], b_miny[kBins], b_maxx[kBins], b_maxy[kBins], b_area[kBins];
   __shared__ unsigned long long b_sx[kBins], b_sy[kBins];
+  // gpi workgroups per image of npix pixels. With node_ptr (a batch) image b's labels own the
+  // rows [node_ptr[b], node_ptr[b + 1]) of the n rows; offsets that leave them own none.
+  const int img = blockIdx.x / gpi, blk = blockIdx.x - img * gpi;
+  labels += (int64_t)img * npix;
+  if (node_ptr) {
+    const int64_t r0 = node_ptr[img], r1 = node_ptr[img + 1];
+    const bool ok = r0 >= 0 && r0 <= r1 && r1 <= n;
+    n = ok ? (int)(r1 - r0) : 0;
+    stats += (ok ? r0 : 0) * 5;
+    sums += (ok ? r0 : 0) * 2;
+  }
   const int nb = min(n, kBins);
   for (int i = threadIdx.x; i < nb; i += kThreads) {
     b_minx[i] = INT_MAX;
@@ -313,7 +344,7 @@ __global__ void __launch_bounds__(kThreads)
   int bad = 0;
   for (int c = 0; c < chunks; ++c) {
     const int64_t p0 =
-        ((int64_t)blockIdx.x * chunks + c) * (kThreads * kRun) + (int64_t)threadIdx.x * kRun;
+        ((int64_t)blk * chunks + c) * (kThreads * kRun) + (int64_t)threadIdx.x * kRun;
     if (p0 >= npix) break;
     int y = (int)(p0 / W), x = (int)(p0 - (int64_t)y * W);
     int cur = -1, minx = 0, maxx = 0, miny = 0, maxy = 0, area = 0;
@@ -404,33 +435,108 @@ __global__ void __launch_bounds__(kThreads)
   centroids[2 * (int64_t)i + 1] = (double)(long long)sy / (double)area;
 }
 
+// ---- launches: one image (lgnn_label_pool, lgnn_ccl, lgnn_ccl_stats below) or a batch of equal
+// ---- size (ccl_batch.hip); arguments are checked by the entries -------------------------------
+
+bool image_dims_ok(int H, int W) {
+  return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31);
+}
+bool batch_dims_ok(int B, int H, int W) {
+  return B > 0 && image_dims_ok(H, W) && (int64_t)B * H * W < ((int64_t)1 << 31);
+}
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int launch_label_pool(const float* logits, int B, int K, int Hin, int Win, uint8_t* out, int H,
+                      int W, hipStream_t s) {
+  const int64_t npix = (int64_t)B * H * W;
+  hipLaunchKernelGGL(k_label_pool, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, s, logits, B, K, Hin, Win, out, H, W);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+size_t ccl_workspace_bytes(int B, int H, int W) {
+  const int64_t hw = (int64_t)H * W;
+  const int64_t nb = B * ((hw + kScanPix - 1) / kScanPix);
+  return 2 * align256((size_t)(B * hw) * sizeof(int32_t)) + align256((size_t)nb * sizeof(int32_t));
+}
+
+// The batch is one image of B * H rows in which no link crosses a multiple of H, its roots
+// counted and ranked in blocks that end with each image. num_labels [B]; node_ptr [B + 1] or NULL.
+int launch_ccl(const uint8_t* image, int B, int H, int W, int connectivity, int64_t* labels,
+               int32_t* num_labels, int64_t* node_ptr, void* workspace, hipStream_t s) {
+  const int64_t hw = (int64_t)H * W, npix = B * hw;
+  const int rows = B * H;
+  const int nbi = (int)((hw + kScanPix - 1) / kScanPix), nb = B * nbi;
+  char* ws = static_cast<char*>(workspace);
+  int32_t* parent = reinterpret_cast<int32_t*>(ws);
+  ws += align256((size_t)npix * sizeof(int32_t));
+  int32_t* rootlabel = reinterpret_cast<int32_t*>(ws);
+  ws += align256((size_t)npix * sizeof(int32_t));
+  int32_t* blockcount = reinterpret_cast<int32_t*>(ws);
+
+  const int nseg = (W + kSeg - 1) / kSeg;
+  const dim3 sgrid((unsigned)(((int64_t)rows * nseg + kWaves - 1) / kWaves));
+  hipLaunchKernelGGL(k_ccl_init, sgrid, dim3(kThreads), 0, s, image, rows, W, nseg, parent);
+  LGNN_LAUNCH_CHECK();
+  if (connectivity == 8)
+    hipLaunchKernelGGL(k_ccl_merge<true>, sgrid, dim3(kThreads), 0, s, image, rows, H, W, nseg,
+                       parent);
+  else
+    hipLaunchKernelGGL(k_ccl_merge<false>, sgrid, dim3(kThreads), 0, s, image, rows, H, W, nseg,
+                       parent);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_compress, dim3(nb), dim3(kThreads), 0, s, parent, hw, nbi, blockcount);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_scan, dim3(1), dim3(kScanThreads), 0, s, blockcount, nb, nbi, B,
+                     num_labels, node_ptr);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_rank, dim3(nb), dim3(kThreads), 0, s, parent, hw, nbi, blockcount,
+                     rootlabel);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ccl_label, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
+                     dim3(kThreads), 0, s, parent, rootlabel, npix, labels);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+// labels [B, H, W] -> num_rows rows of stats and centroids: the rows of image b start at
+// node_ptr[b] (device), or at 0 for the one image of node_ptr == NULL.
+int launch_ccl_stats(const int64_t* labels, int B, int H, int W, const int64_t* node_ptr,
+                     int num_rows, int32_t* stats, double* centroids, int32_t* err,
+                     hipStream_t s) {
+  const int64_t hw = (int64_t)H * W;
+  unsigned long long* sums = reinterpret_cast<unsigned long long*>(centroids);
+  const dim3 lgrid((unsigned)((num_rows + kThreads - 1) / kThreads));
+  hipLaunchKernelGGL(k_stats_init, lgrid, dim3(kThreads), 0, s, num_rows, stats, sums, err);
+  LGNN_LAUNCH_CHECK();
+  const int64_t chunk = (int64_t)kThreads * kRun;
+  const int64_t nchunks = (hw + chunk - 1) / chunk;
+  const int gpi = (int)std::min<int64_t>(nchunks, 1024);
+  const int chunks = (int)((nchunks + gpi - 1) / gpi);
+  hipLaunchKernelGGL(k_stats_acc, dim3((unsigned)((int64_t)B * gpi)), dim3(kThreads), 0, s,
+                     labels, hw, W, num_rows, chunks, gpi, node_ptr, stats, sums, err);
+  LGNN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_stats_finish, lgrid, dim3(kThreads), 0, s, num_rows, stats, centroids);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
 }  // namespace lgnn_cclk
 
 using namespace lgnn_cclk;
-
-static bool image_dims_ok(int H, int W) {
-  return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31);
-}
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" int lgnn_label_pool(const float* logits, int classes, int in_height, int in_width,
                                uint8_t* out, int height, int width, void* stream) {
   if (classes < 1 || classes > 255 || !image_dims_ok(in_height, in_width) ||
       !image_dims_ok(height, width) || !logits || !out)
     return LGNN_EINVAL;
-  const int64_t npix = (int64_t)height * width;
-  hipLaunchKernelGGL(k_label_pool, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, as_stream(stream), logits, classes, in_height, in_width,
-                     out, height, width);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch_label_pool(logits, 1, classes, in_height, in_width, out, height, width,
+                           as_stream(stream));
 }
 
 extern "C" size_t lgnn_ccl_workspace_bytes(int height, int width) {
-  if (!image_dims_ok(height, width)) return 0;
-  const int64_t npix = (int64_t)height * width;
-  const int64_t nb = (npix + kScanPix - 1) / kScanPix;
-  return 2 * align256((size_t)npix * sizeof(int32_t)) + align256((size_t)nb * sizeof(int32_t));
+  return image_dims_ok(height, width) ? ccl_workspace_bytes(1, height, width) : 0;
 }
 
 extern "C" int lgnn_ccl(const uint8_t* image, int height, int width, int connectivity,
@@ -440,58 +546,15 @@ extern "C" int lgnn_ccl(const uint8_t* image, int height, int width, int connect
   if (!image || !labels || !num_labels || !workspace ||
       workspace_bytes < lgnn_ccl_workspace_bytes(height, width))
     return LGNN_EINVAL;
-  hipStream_t s = as_stream(stream);
-  const int64_t npix = (int64_t)height * width;
-  const int nb = (int)((npix + kScanPix - 1) / kScanPix);
-  char* ws = static_cast<char*>(workspace);
-  int32_t* parent = reinterpret_cast<int32_t*>(ws);
-  ws += align256((size_t)npix * sizeof(int32_t));
-  int32_t* rootlabel = reinterpret_cast<int32_t*>(ws);
-  ws += align256((size_t)npix * sizeof(int32_t));
-  int32_t* blockcount = reinterpret_cast<int32_t*>(ws);
-
-  const int nseg = (width + kSeg - 1) / kSeg;
-  const dim3 sgrid((unsigned)(((int64_t)height * nseg + kWaves - 1) / kWaves));
-  hipLaunchKernelGGL(k_ccl_init, sgrid, dim3(kThreads), 0, s, image, height, width, nseg, parent);
-  LGNN_LAUNCH_CHECK();
-  if (connectivity == 8)
-    hipLaunchKernelGGL(k_ccl_merge<true>, sgrid, dim3(kThreads), 0, s, image, height, width, nseg,
-                       parent);
-  else
-    hipLaunchKernelGGL(k_ccl_merge<false>, sgrid, dim3(kThreads), 0, s, image, height, width,
-                       nseg, parent);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_compress, dim3(nb), dim3(kThreads), 0, s, parent, npix, blockcount);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_scan, dim3(1), dim3(kScanThreads), 0, s, blockcount, nb, num_labels);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_rank, dim3(nb), dim3(kThreads), 0, s, parent, npix, blockcount,
-                     rootlabel);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_label, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, s, parent, rootlabel, npix, labels);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch_ccl(image, 1, height, width, connectivity, labels, num_labels, nullptr, workspace,
+                    as_stream(stream));
 }
 
 extern "C" int lgnn_ccl_stats(const int64_t* labels, int height, int width, int num_labels,
                               int32_t* stats, double* centroids, int32_t* err, void* stream) {
   if (!image_dims_ok(height, width) || num_labels < 1) return LGNN_EINVAL;
   if (!labels || !stats || !centroids || !err) return LGNN_EINVAL;
-  hipStream_t s = as_stream(stream);
-  const int64_t npix = (int64_t)height * width;
-  unsigned long long* sums = reinterpret_cast<unsigned long long*>(centroids);
-  const dim3 lgrid((unsigned)((num_labels + kThreads - 1) / kThreads));
-  hipLaunchKernelGGL(k_stats_init, lgrid, dim3(kThreads), 0, s, num_labels, stats, sums, err);
-  LGNN_LAUNCH_CHECK();
-  const int64_t chunk = (int64_t)kThreads * kRun;
-  const int64_t nchunks = (npix + chunk - 1) / chunk;
-  const int grid = (int)std::min<int64_t>(nchunks, 1024);
-  const int chunks = (int)((nchunks + grid - 1) / grid);
-  hipLaunchKernelGGL(k_stats_acc, dim3(grid), dim3(kThreads), 0, s, labels, npix, width,
-                     num_labels, chunks, stats, sums, err);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_stats_finish, lgrid, dim3(kThreads), 0, s, num_labels, stats, centroids);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch_ccl_stats(labels, 1, height, width, nullptr, num_labels, stats, centroids, err,
+                          as_stream(stream));
 }
+

@@ -9,7 +9,9 @@ a timm encoder from the HF hub) needs network weights and image data and is out 
 (lgnn_label_pool), labels its connected components and takes their centroids (lgnn_ccl,
 lgnn_ccl_stats: `connected_components_with_stats`, in place of OpenCV on the host), and pools
 the features per component (`extract_features_by_cc`, :88-93, lgnn_cc_pool) into the d_in =
-encoder channels + 1 node features.
+encoder channels + 1 node features. `nodes_from_batch` does the same for a batch of images in one
+pass (lgnn_label_pool_batch, lgnn_ccl_batch, lgnn_ccl_stats_batch) and pools the features where
+`reinterpolation` would put them without interpolating them first (lgnn_cc_pool_resample).
 """
 from __future__ import annotations
 
@@ -106,10 +108,43 @@ class LesionNodes:
     edge_attr: torch.Tensor | None = None
 
 
+@dataclasses.dataclass
+class LesionNodesBatch:
+    """The lesion nodes of B images, flat (`LesionsExtractor.nodes_from_batch`): image b owns the
+    rows [ptr[b], ptr[b + 1]). `batch[b]` is that image's `LesionNodes`, holding views into the
+    batch; `to_store()` hands the tensors to a `GraphStore` as they are."""
+
+    x: torch.Tensor    # [sum n, C + 1] fp32
+    pos: torch.Tensor  # [sum n, 2] fp64
+    y: torch.Tensor    # [B] int64, on the host like LesionNodes.y
+    ptr: torch.Tensor  # [B + 1] int64 on the device
+    names: list | None = None
+    ptr_host: torch.Tensor | None = None  # the host copy nodes_from_batch read
+
+    def __post_init__(self):
+        if self.ptr_host is None:
+            self.ptr_host = self.ptr.cpu()
+
+    def __len__(self) -> int:
+        return self.ptr_host.numel() - 1
+
+    def __getitem__(self, b: int) -> LesionNodes:
+        b = range(len(self))[b]
+        lo, hi = int(self.ptr_host[b]), int(self.ptr_host[b + 1])
+        return LesionNodes(pos=self.pos[lo:hi], x=self.x[lo:hi], y=self.y[b:b + 1],
+                           name=None if self.names is None else self.names[b])
+
+    def to_store(self):
+        from ..memory import GraphStore
+
+        return GraphStore.from_tensors(self.x, self.pos, self.y, self.ptr_host)
+
+
 class LesionsExtractor:
     """Reference LesionsExtractor (lesions.py:96-186) from the segmentation output on:
-    `nodes_from_maps` is lines 147-176 on the GPU. The segmentation model, the timm encoder and
-    image loading are not part of this package, so `__call__` raises."""
+    `nodes_from_maps` is lines 147-176 on the GPU, `nodes_from_batch` the same for a batch of
+    images in one pass. The segmentation model, the timm encoder and image loading are not part
+    of this package, so `__call__` raises."""
 
     def __init__(self, config: LesionsNodesConfig):
         self.feature_source = config.feature_source
@@ -163,6 +198,67 @@ class LesionsExtractor:
             ops.cc_pool(classes.reshape(1, H * W).float(), lab, nlabel, reduce_max,
                         validate=False)], dim=1)
         return LesionNodes(pos=centroids, x=x, y=torch.tensor([label]), name=name)
+
+    @torch.no_grad()
+    def nodes_from_batch(self, label_maps: torch.Tensor, features: torch.Tensor, labels,
+                         names=None) -> LesionNodesBatch:
+        """`nodes_from_maps` for B images at once: label_maps (B, K, Horg, Worg) fp32 logits,
+        features (B, C, h, w) fp32, both on the GPU, labels the B graph labels, names B names or
+        None. The features are not interpolated to `reinterpolation`: the pooling samples them
+        there as it reads (lgnn_cc_pool_resample), so no (B, C, H, W) tensor exists. The launch
+        count does not depend on B, and the host reads the device once: the B + 1 node offsets,
+        which size the outputs."""
+        from ... import _lib, ops
+
+        _lib.require_gpu(label_maps, features)
+        if label_maps.dim() != 4:
+            raise ValueError("label_maps must be (B, K, H, W)")
+        if features.dim() != 4:
+            raise ValueError("features must be (B, C, h, w)")
+        B = label_maps.size(0)
+        if features.size(0) != B:
+            raise ValueError(f"label_maps holds {B} images, features {features.size(0)}")
+        y = torch.as_tensor(labels, dtype=torch.int64, device="cpu").reshape(-1)
+        if y.numel() != B:
+            raise ValueError(f"{y.numel()} labels for {B} images")
+        if names is not None:
+            names = list(names)
+            if len(names) != B:
+                raise ValueError(f"{len(names)} names for {B} images")
+        Horg = label_maps.size(2)
+        C = features.size(1)
+        H, W = self.reinterpolation if self.reinterpolation is not None else features.shape[2:]
+        classes = ops.label_pool_batch(label_maps, (H, W))
+        cc, _, ptr = ops.ccl_batch(classes, connectivity=8)
+        ptr_host = ptr.cpu()  # the one host read
+        sizes = ptr_host[1:] - ptr_host[:-1]
+        limit = _lib.LGNN_CC_POOL_MAX_SEGMENTS
+        if int(sizes.max()) > limit:
+            b = int(sizes.argmax())
+            raise ValueError(f"image {b}: {int(sizes[b])} components (background included) "
+                             f"exceed the {limit} segments lgnn_cc_pool_resample takes")
+        total, nmax = int(ptr_host[-1]), int(sizes.max())
+        _, centroids = ops.ccl_stats_batch(cc, ptr, total, validate=False)
+        # the same tensor divisor as nodes_from_maps
+        centroids = (centroids * Horg) / torch.full_like(centroids, H)
+        reduce_max = self.features_reduction == FeaturesReduction.MAX
+        cls = classes.view(B, 1, H, W).float()
+
+        def pool(f, c, lab, p, n, mx, rmax):
+            return torch.cat([
+                ops.cc_pool_resample(f, lab, p, n, rmax, max_nodes=mx, validate=False),
+                ops.cc_pool_resample(c, lab, p, n, rmax, max_nodes=mx, validate=False)], dim=1)
+
+        x = pool(features, cls, cc, ptr, total, nmax, reduce_max)
+        lone = torch.nonzero(sizes == 1).reshape(-1)
+        if reduce_max and lone.numel():
+            # an image that is all background has one node, which the reference gives the mean
+            # (nlabel == 1 in extract_features_by_cc), also under MAX
+            idx = lone.to(x.device)
+            sub_ptr = torch.arange(lone.numel() + 1, dtype=torch.int64).to(x.device)
+            x[ptr_host[lone].to(x.device)] = pool(features[idx], cls[idx], cc[idx], sub_ptr,
+                                                  lone.numel(), 1, False)
+        return LesionNodesBatch(x=x, pos=centroids, y=y, ptr=ptr, names=names, ptr_host=ptr_host)
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}(feature_source={self.feature_source})"

@@ -2309,6 +2309,118 @@ def ccl_stats(labels: torch.Tensor, num_labels: int,
     return stats, centroids
 
 
+def label_pool_batch(logits: torch.Tensor, size: tuple[int, int]) -> torch.Tensor:
+    """logits (B, K, Hin, Win) fp32, K <= 255 -> (B, H, W) uint8: `label_pool` of every image, in
+    one launch (lgnn_label_pool_batch)."""
+    _lib.require_gpu(logits)
+    if logits.dim() != 4:
+        raise ValueError("logits must be (B, K, H, W)")
+    f = _f32c(logits)
+    B, K, Hin, Win = f.shape
+    if not 1 <= K <= 255:
+        raise ValueError("label_pool_batch takes 1 to 255 classes")
+    H, W = int(size[0]), int(size[1])
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=f.device)
+    _lib.call("lgnn_label_pool_batch", f, B, K, Hin, Win, out, H, W, _s(f.device))
+    return out
+
+
+def ccl_batch(image: torch.Tensor, connectivity: int = 8
+              ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """image (B, H, W) uint8, nonzero = foreground -> (labels (B, H, W) int64, num_labels int32
+    [B], node_ptr int64 [B + 1], all on the device): per image what `ccl` gives for it alone,
+    the numbering restarting in every image; node_ptr is the exclusive scan of num_labels
+    (lgnn_ccl_batch). Six launches whatever B is, no host synchronisation."""
+    _lib.require_gpu(image)
+    if image.dim() != 3 or image.dtype != torch.uint8:
+        raise ValueError("image must be a (B, H, W) uint8 tensor")
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    img = image.contiguous()
+    B, H, W = img.shape
+    dev = img.device
+    labels = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+    num = torch.empty(B, dtype=torch.int32, device=dev)
+    node_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    nws = _lib.load().lgnn_ccl_batch_workspace_bytes(B, H, W)
+    ws = torch.empty(max(1, nws), dtype=torch.uint8, device=dev)
+    _lib.call("lgnn_ccl_batch", img, B, H, W, int(connectivity), labels, num, node_ptr, ws, nws,
+              _s(dev))
+    return labels, num, node_ptr
+
+
+def ccl_stats_batch(labels: torch.Tensor, node_ptr: torch.Tensor, total_nodes: int,
+                    validate: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """labels (B, H, W) int64 and node_ptr int64 [B + 1] as `ccl_batch` gives them, total_nodes =
+    node_ptr[B] -> (stats (total_nodes, 5) int32, centroids (total_nodes, 2) fp64): row
+    node_ptr[b] + l is `ccl_stats`' row l for image b (lgnn_ccl_stats_batch). validate: raise if
+    a label falls outside its image's range (one host read)."""
+    _lib.require_gpu(labels, node_ptr)
+    if labels.dim() != 3 or labels.dtype != torch.int64:
+        raise ValueError("labels must be a (B, H, W) int64 tensor")
+    lab = labels.contiguous()
+    B, H, W = lab.shape
+    if node_ptr.dtype != torch.int64 or node_ptr.numel() != B + 1:
+        raise ValueError("node_ptr must be an int64 tensor of B + 1 offsets")
+    dev = lab.device
+    n = int(total_nodes)
+    stats = torch.empty(n, 5, dtype=torch.int32, device=dev)
+    centroids = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_ccl_stats_batch", lab, B, H, W, node_ptr.contiguous(), n, stats, centroids,
+              err, _s(dev))
+    if validate and int(err.item()):
+        raise IndexError(f"ccl_stats_batch: {int(err.item())} labels outside their image's range")
+    return stats, centroids
+
+
+def cc_pool_resample(features: torch.Tensor, labels: torch.Tensor, node_ptr: torch.Tensor,
+                     total_nodes: int, reduce_max: bool, max_nodes: int | None = None,
+                     validate: bool = True, return_counts: bool = False):
+    """features (B, C, h, w) fp32, labels (B, H, W) int64 and node_ptr int64 [B + 1] as
+    `ccl_batch` gives them, total_nodes = node_ptr[B] -> (total_nodes, C): row node_ptr[b] + l
+    is the mean or max, over the pixels of label l of image b, of the feature map sampled
+    bilinearly at (H, W) (F.interpolate's align_corners=False), which is never stored
+    (lgnn_cc_pool_resample); (H, W) == (h, w) pools the map itself. h * w * 4 <=
+    LGNN_CC_POOL_RESAMPLE_MAX_SOURCE_BYTES unless the sizes are equal. max_nodes: an upper bound
+    of the labels per image the caller knows (default: the limit, 4032); a tight one runs
+    faster. validate: raise if a label falls outside its image's range (one host read).
+    return_counts: also the pixels per label, (total_nodes,) int32."""
+    _lib.require_gpu(features, labels, node_ptr)
+    if features.dim() != 4:
+        raise ValueError("features must be (B, C, h, w)")
+    if labels.dim() != 3 or labels.dtype != torch.int64:
+        raise ValueError("labels must be a (B, H, W) int64 tensor")
+    f = _f32c(features)
+    lab = labels.contiguous()
+    B, C, h, w = f.shape
+    H, W = lab.shape[1:]
+    if lab.size(0) != B:
+        raise ValueError("features and labels must hold the same number of images")
+    if node_ptr.dtype != torch.int64 or node_ptr.numel() != B + 1:
+        raise ValueError("node_ptr must be an int64 tensor of B + 1 offsets")
+    limit = _lib.LGNN_CC_POOL_MAX_SEGMENTS
+    nmax = limit if max_nodes is None else int(max_nodes)
+    if not 1 <= nmax <= limit:
+        raise ValueError(f"max_nodes must be in [1, {limit}]")
+    if (h, w) != (H, W) and h * w * 4 > _lib.LGNN_CC_POOL_RESAMPLE_MAX_SOURCE_BYTES:
+        raise ValueError(f"cc_pool_resample stages a source map of at most "
+                         f"{_lib.LGNN_CC_POOL_RESAMPLE_MAX_SOURCE_BYTES} bytes, got {h} x {w}")
+    dev = f.device
+    n = int(total_nodes)
+    out = torch.empty(n, C, dtype=torch.float32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev) if return_counts else None
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    nws = _lib.load().lgnn_cc_pool_resample_workspace_bytes(B, H, W, n)
+    ws = torch.empty(max(1, nws), dtype=torch.uint8, device=dev)
+    _lib.call("lgnn_cc_pool_resample", f, B, C, h, w, lab, H, W, node_ptr.contiguous(), n, nmax,
+              int(reduce_max), out, counts, err, ws, nws, _s(dev))
+    if validate and int(err.item()):
+        raise IndexError(f"cc_pool_resample: {int(err.item())} labels outside their image's "
+                         f"range or at or above max_nodes = {nmax}")
+    return (out, counts) if return_counts else out
+
+
 def collate(store, ids, validate: bool = False):
     """The graphs `ids` (host int64 tensor or list; repeats allowed) of a datasets.GraphStore as
     one synth.Batch on the store's device (lgnn_collate): x, pos, y, batch, ptr as PyG's Collater
