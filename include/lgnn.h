@@ -129,8 +129,17 @@ int lgnn_graph_build_lazy(const int64_t* edge_index, int64_t E, int64_t N, int l
  * weight planes of `job` (what lgnn_weight_planes(job->nl, job->W, job->widths, job->planes,
  * job->planes_t) writes, bitwise) as extra workgroups: the planes a fused GCN stack forward reads
  * are made from the live weights by every forward that builds its graph, with no launch of their
- * own (a captured step replays the split, so weights written between replays are seen). */
+ * own (a captured step replays the split, so weights written between replays are seen).
+ *
+ * Fold slot: with LGNN_PLANE_JOB_FOLD OR-ed into nl (layers = nl without the flag, 2 <= layers <=
+ * LGNN_PLANE_JOB_MAX - 1) W[layers] points to b_0 [widths[1]], in_proj's bias, and the job also
+ * writes, behind the layers' slots of `planes`, one more slot: the planes of W_10 = W_1 W_0
+ * ([widths[2]][widths[0]], fp32 fmaf sums over j ascending: the same bits whichever launch runs the
+ * job) and behind it 128 floats b_10 = W_1 b_0 (zero past widths[2]) — in_proj folded into conv 1,
+ * read by lgnn_gcn_stack_fwd_s3(_all) with has_in_proj = LGNN_S3_FWD_FOLD / _FOLD_H0. `planes` then
+ * holds lgnn_weight_planes_bytes(nl) bytes with the flag in nl; planes_t is as without it. */
 #define LGNN_PLANE_JOB_MAX 8
+#define LGNN_PLANE_JOB_FOLD 256
 typedef struct lgnn_plane_job {
   int nl;                                /* layers, 1..LGNN_PLANE_JOB_MAX */
   int widths[LGNN_PLANE_JOB_MAX + 1];    /* W[l] is [widths[l+1]][widths[l]] */
@@ -497,8 +506,23 @@ int lgnn_gcn_stack_fwd(const float* X, int64_t M, int d_in, int has_in_proj,
  * weights of layers 0..L as written by lgnn_weight_planes (in place of W). L >= 1.
  * adjt (nullable): ceil(M/64) * LGNN_S3_ADJT_TILE_BYTES bytes; receives, for every closed tile,
  * the tile's dense fp32 Â (64 x 64, as summed from the CSR block), which
- * lgnn_gcn_stack_bwd_s3f(_all) then loads instead of rebuilding it (same graph, same tile_open). */
+ * lgnn_gcn_stack_bwd_s3f(_all) then loads instead of rebuilding it (same graph, same tile_open).
+ * has_in_proj here (and in lgnn_gcn_stack_fwd_s3_all) selects how the closed tiles run; any other
+ * value is LGNN_EINVAL:
+ *   0, 1                  as lgnn_gcn_stack_fwd: without / with in_proj as a GEMM of its own
+ *   LGNN_S3_FWD_FOLD      in_proj folded into conv 1 (exact: no activation between them):
+ *                         H_1 = ELU(Â (X W_10^T + 1 b_10^T) + b_1) from the fold slot of `planes`
+ *                         (a plane job with LGNN_PLANE_JOB_FOLD, L + 1 <= LGNN_PLANE_JOB_MAX - 1);
+ *                         H[0] rows of closed tiles are NOT written (open tiles' rows are). For a
+ *                         backward that does not read H_0 (lgnn_gcn_stack_bwd_s3f* with H[0] NULL).
+ *   LGNN_S3_FWD_FOLD_H0   the same H_1..H_L, bit for bit, and H[0] of the closed tiles also
+ *                         formed and stored as with has_in_proj = 1 (bit for bit).
+ * Open tiles run in_proj and every conv on the fp32 weights in all modes: b[0], H[0] (and W[0] for
+ * _all) stay required. H_1..H_L of the folded modes differ from has_in_proj = 1 at fp32 rounding
+ * level (another association of the same sums). */
 #define LGNN_S3_ADJT_TILE_BYTES 16384
+#define LGNN_S3_FWD_FOLD 2
+#define LGNN_S3_FWD_FOLD_H0 3
 int lgnn_gcn_stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
                           const int32_t* rowptr, const int32_t* col, const float* w, int L,
                           const uint16_t* planes, const float* const* b, const int* widths,
@@ -506,7 +530,10 @@ int lgnn_gcn_stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
 /* Weight planes for the split-3 kernels: nl layers, W[l] [widths[l+1], widths[l]] fp32
  * (torch Linear layout; widths <= 128, multiples of 4) -> planes[l][3][128][128] bf16 (zero
  * padded, feature order perm16), lgnn_weight_planes_bytes(nl) bytes; planes_t (nullable, same
- * size) also gets the transposed planes. One launch; rerun whenever the weights change. */
+ * size) also gets the transposed planes. One launch; rerun whenever the weights change.
+ * nl may carry LGNN_PLANE_JOB_FOLD (see lgnn_plane_job): W then has layers + 1 entries, the last
+ * one b_0, and `planes` also receives the fold slot and b_10 (lgnn_weight_planes_bytes(nl) with
+ * the flag counts them). */
 size_t lgnn_weight_planes_bytes(int nl);
 int lgnn_weight_planes(int nl, const float* const* W, const int* widths, uint16_t* planes,
                        uint16_t* planes_t, void* stream);
@@ -698,7 +725,8 @@ int lgnn_gcn_stack_bwd_s3f(const float* dP, const int64_t* batch, const int32_t*
  * Both _all entries return LGNN_EBUSY (nothing launched) when the device cannot hold every
  * workgroup of the launch at once (its grid barriers need co-residency): the caller then runs the
  * open tiles in separate launches. lgnn_fused_grid_capacity(which) = workgroups resident at once
- * (occupancy per CU x CUs; which 0 = forward, 1 = backward), or an error code (< 0). A barrier
+ * (occupancy per CU x CUs; which 0 = forward, the smallest over its has_in_proj variants — the
+ * launch checks the variant it runs —, 1 = backward), or an error code (< 0). A barrier
  * that still times out (~0.5 s) counts itself in the third barrier word (tile_open[ntiles + 3]
  * forward, [ntiles + 6] backward), which stays set until the next graph build zeroes it.
  * ------------------------------------------------------------------------------------------- */

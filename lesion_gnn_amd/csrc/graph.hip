@@ -146,6 +146,7 @@ __device__ __forceinline__ void prep_body(int32_t* __restrict__ zero, int64_t nz
 }
 
 // workgroups past the build's own grid (gx) run the weight-plane side job (lgnn_graph_build_planes)
+static_assert(kThreads == lgnn_s3::FOLD_NT, "the fold slot is run by whole 256-thread workgroups");
 __device__ __forceinline__ bool plane_side_job(const lgnn_s3::PlaneArgs& pj, int gx) {
   if ((int)blockIdx.x < gx) return false;
   lgnn_s3::wplanes_item(pj, ((int)blockIdx.x - gx) * kThreads + threadIdx.x);
@@ -1100,8 +1101,9 @@ extern "C" int lgnn_graph_build_planes(const int64_t* edge_index, int64_t E, int
                                        void* workspace, size_t workspace_bytes, int lazy,
                                        const lgnn_plane_job* job, void* stream) {
   if (lazy && (!tile_open || !tptr || tmap)) return LGNN_EINVAL;
-  if (!job || job->nl > LGNN_PLANE_JOB_MAX) return LGNN_EINVAL;
-  lgnn_s3::PlaneArgs pj;
+  if (!job || job->nl < 1 || (job->nl & ~LGNN_PLANE_JOB_FOLD) > LGNN_PLANE_JOB_MAX)
+    return LGNN_EINVAL;
+  lgnn_s3::PlaneArgs pj;  // (with LGNN_PLANE_JOB_FOLD in nl: W[layers] = b_0, the fold slot too)
   const int r = lgnn_s3::plane_args(job->nl, job->W, job->widths, job->planes, job->planes_t, pj);
   if (r != LGNN_OK) return r;
   return graph_build(edge_index, E, N, loops, norm, rowptr, col, w, tptr, tidx, tw, tmap,
@@ -1163,7 +1165,8 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
   // the weight-plane side job rides the first launch as extra workgroups
   lgnn_s3::PlaneArgs pj{};
   if (planes) pj = *planes;
-  const int pblocks = planes ? (pj.nl * lgnn_s3::PLANE_ITEMS + kThreads - 1) / kThreads : 0;
+  const int pblocks =
+      planes ? (lgnn_s3::plane_items(pj) + kThreads - 1) / kThreads : 0;
   // target-sorted fast path: only for builds without the source CSR (or lazily with it) and
   // without tmap
   SortedArgs sa{};

@@ -109,7 +109,8 @@ __device__ __forceinline__ int frag_index(int row, int phys) {
 //   Wp[l][plane][n / 32][s][h][n % 32][8]  holds  phys positions 16 s + 8 h .. + 7 of row n
 // (lane h * 32 + n % 32 of wave n / 32 loads k-step s with one 16-B load). With WpT also the
 // transposed planes (rows k, positions perm16(n)) in the same order: the backward's dH = G W_l
-// operand. Item i = one (layer, n, 4 consecutive k); nl * PLANE_ITEMS items in all. Run by
+// operand. Item i = one (slot, n, 4 consecutive k), plane_items() in all: the nl layers' and, with
+// b0, the fold slot's (W_10 = W_1 W_0, its fp32 b_10 behind it). Run by
 // k_wplanes (stack3.hip) or as side work of the graph build's first launch (graph.hip).
 struct PlaneArgs {
   const float* W[LGNN_MAX_STACK];
@@ -118,14 +119,88 @@ struct PlaneArgs {
   int nl;
   uint16_t* Wp;
   uint16_t* WpT;  // nullable
+  const float* b0;  // fold slot (LGNN_PLANE_JOB_FOLD): in_proj's bias; nullptr = no fold slot
 };
 constexpr int PLANE_ITEMS = WP * WP / 4;  // items per layer
+// items of the job: the layers' and, with the fold, the fold slot's
+__host__ __device__ inline int plane_items(const PlaneArgs& a) {
+  return (a.nl + (a.b0 ? 1 : 0)) * PLANE_ITEMS;
+}
+// the fold slot's fp32 b_10 [WP], behind its planes
+__host__ __device__ inline float* fold_bias(uint16_t* Wp, int nl) {
+  return reinterpret_cast<float*>(Wp + (size_t)(nl + 1) * 3 * PLANE);
+}
+
+// Fold slot, item (n, 4 consecutive k): W_10 = W_1 W_0 (in_proj folded into conv 1, exact: no
+// activation between them), W_10[n][k..k+3] = sum_j W_1[n][j] W_0[j][k..k+3] in fp32 fmaf, j
+// ascending (a fixed order: the same bits from every launch that runs the job), split like any
+// other slot; the k == 0 items also write b_10[n] = sum_j W_1[n][j] b_0[j] as fp32 behind it.
+// Run by whole 256-thread workgroups (a slot's items start at a multiple of 256: the slot test
+// is block-uniform), 8 rows n each. The sums are 128 terms long, so nothing is loaded inside
+// them: the workgroup's 8 rows of W_1, b_0 and W_0 (two halves of 64 rows, 36.5 KiB of LDS in
+// all) are fetched by loads that are all in flight at once, each element once per workgroup, and
+// the fmaf chains read LDS. (A global load per term costs a memory round trip per term and
+// every W_0 element is wanted by 128 rows: that form held the build's first launch for 25 us.)
+constexpr int FOLD_NT = 256;   // threads per workgroup of every kernel that runs the job
+constexpr int FOLD_HALF = 64;  // rows of W_0 staged at a time
+struct FoldSmem {
+  float w0[FOLD_HALF][WP];
+  float w1[FOLD_NT / (WP / 4)][WP];
+  float b0[WP];
+};
+__device__ __forceinline__ void wplanes_fold_item(const PlaneArgs& a, int n, int k) {
+  __shared__ __attribute__((aligned(16))) FoldSmem sm;
+  const int K = a.K[0], J = a.N[0], N = a.N[1];  // W_0 [J][K], W_1 [N][J]; all multiples of 4
+  // (k = 4 (threadIdx.x % 32), n = the workgroup's first row + threadIdx.x / 32)
+  const int t = threadIdx.x, tr = t / (WP / 4);
+  constexpr int PER = FOLD_HALF * WP / 4 / FOLD_NT;  // float4 of a half per thread
+  // every load up front; what lies past a width is zero, so the padding needs no branch below
+  f32x4 g[2][PER];
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int j = FOLD_HALF * h + tr + (FOLD_NT / (WP / 4)) * u;
+      g[h][u] = (j < J && k < K) ? ld4(a.W[0] + (int64_t)j * K + k) : zero4();
+    }
+  st4(&sm.w1[tr][k], (n < N && k < J) ? ld4(a.W[1] + (int64_t)n * J + k) : zero4());
+  if (t < WP / 4) st4(&sm.b0[k], k < J ? ld4(a.b0 + k) : zero4());
+  f32x4 v = zero4();
+  float s = 0.f;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (h) __syncthreads();  // the first half is read
+#pragma unroll
+    for (int u = 0; u < PER; ++u) st4(&sm.w0[tr + (FOLD_NT / (WP / 4)) * u][k], g[h][u]);
+    __syncthreads();
+    const int je = J - FOLD_HALF * h < FOLD_HALF ? J - FOLD_HALF * h : FOLD_HALF;
+    for (int j = 0; j < je; j += 4) {
+      const f32x4 c = ld4(&sm.w1[tr][FOLD_HALF * h + j]);
+      const f32x4 bq = ld4(&sm.b0[FOLD_HALF * h + j]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f32x4 r = ld4(&sm.w0[j + u][k]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = fmaf(c[u], r[q], v[q]);
+        s = fmaf(c[u], bq[u], s);
+      }
+    }
+  }
+  u32x2 o[3];
+  split4(v, o);
+  uint16_t* base = a.Wp + (size_t)a.nl * 3 * PLANE;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+    *reinterpret_cast<u32x2*>(base + p * PLANE + frag_index(n, perm16(k))) = o[p];
+  if (k == 0) fold_bias(a.Wp, a.nl)[n] = s;  // (zero past w2)
+}
 static_assert(LGNN_PLANE_JOB_MAX == LGNN_MAX_STACK, "plane job layers");
 
 __device__ __forceinline__ void wplanes_item(const PlaneArgs& a, int i) {
+  if (i >= plane_items(a)) return;
   const int l = i / PLANE_ITEMS;
-  if (l >= a.nl) return;
   const int n = (i / (WP / 4)) % WP, k = 4 * (i % (WP / 4));
+  if (l >= a.nl) return wplanes_fold_item(a, n, k);
   const int N = a.N[l], K = a.K[l];
   const f32x4 v = (n < N && k < K) ? ld4(a.W[l] + (int64_t)n * K + k) : zero4();
   u32x2 o[3];
@@ -148,10 +223,15 @@ __device__ __forceinline__ void wplanes_item(const PlaneArgs& a, int i) {
 }
 
 // host: the plane job of lgnn_weight_planes' arguments (LGNN_EINVAL on a bad shape)
+// nl may carry LGNN_PLANE_JOB_FOLD: W[layers] is then b_0 and the fold slot is written too
 inline int plane_args(int nl, const float* const* W, const int* widths, uint16_t* planes,
                       uint16_t* planes_t, PlaneArgs& a) {
+  const bool fold = nl > 0 && (nl & LGNN_PLANE_JOB_FOLD);
+  if (fold) nl &= ~LGNN_PLANE_JOB_FOLD;
   if (nl < 1 || nl > LGNN_MAX_STACK || !W || !widths || !planes) return LGNN_EINVAL;
+  if (fold && (nl < 2 || nl > LGNN_PLANE_JOB_MAX - 1 || !W[nl])) return LGNN_EINVAL;
   a = PlaneArgs{};
+  a.b0 = fold ? W[nl] : nullptr;
   for (int l = 0; l < nl; ++l) {
     const int K = widths[l], N = widths[l + 1];
     if (!W[l] || K < 4 || N < 4 || K > WP || N > WP || K % 4 || N % 4) return LGNN_EINVAL;

@@ -183,7 +183,13 @@ struct OpenFwdArgs {
                                    // ADJT_TILE_BYTES per tile
 };
 
-template <bool FIRST>
+// MODE (the closed tiles; the open phase depends only on whether in_proj is present):
+//   0  no in_proj: X is H_0                       1  in_proj as a GEMM of its own (legacy)
+//   2  in_proj folded into conv 1: P_1 = X W_10^T + 1 b_10^T from the fold slot of Wp (slot
+//      L + 1, b_10 behind it; W_10 = W_1 W_0, b_10 = W_1 b_0: exact, in_proj has no activation),
+//      taken where mode 1 takes the in_proj GEMM; no H_0 of a closed tile is formed or stored
+//   3  mode 2, and H_0 of the closed tiles also formed as in mode 1 and stored (not re-read)
+template <int MODE>
 __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, int64_t M,
                                                   const int32_t* __restrict__ rowptr,
                                                   const int32_t* __restrict__ col,
@@ -193,14 +199,22 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
                                                   OpenFwdArgs o) {
   __shared__ __attribute__((aligned(16))) FwdSmem sm;
   const int64_t ntiles = (M + TM - 1) / TM;
-  const int l0 = FIRST ? 0 : 1;
-  const int K0 = args.width[l0];
+  constexpr bool FOLD = MODE >= 2;
+  const int l0 = MODE ? 0 : 1;        // first layer of the stack (0: in_proj)
+  const int K0 = args.width[l0];      // X's width
+  // the weight slot a tile starts with: W_1, W_0, or the fold slot
+  const int w_first = MODE == 0 ? 1 : MODE == 2 ? L + 1 : 0;
   float* const scr = reinterpret_cast<float*>(sm.Adj[0]);  // fp32 Â [target][source], 16 KiB
 
   for (int i = threadIdx.x; i < (L + 1) * WP; i += NT) {
     const int l = i / WP, n = i % WP;
     sm.bias[l][n] = (l >= l0 && n < args.width[l + 1]) ? args.b[l][n] : 0.f;
   }
+  // b_10 of this lane's P feature 32 * wave + li (fp32, zero past the width, behind the fold slot)
+  [[maybe_unused]] float b10 = 0.f;
+  if (FOLD)
+    b10 = reinterpret_cast<const float*>(Wp + (size_t)(L + 2) * 3 * PLANE)
+        [32 * (threadIdx.x >> 6) + (threadIdx.x & 31)];
   int64_t t = seek_tile(blockIdx.x, ntiles, tmask, 0);
   if (t < ntiles) {
   [[maybe_unused]] int stamp_i = 0;
@@ -211,7 +225,7 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
   u32x4 wf[3][8];
   const Buf bX = mkbuf(X, M * K0 * 4);
   load_rows(xr, bX, K0, (int)(t * TM));
-  load_wf(wf, Wp, l0);
+  load_wf(wf, Wp, w_first);
   idx_load_head(R, rowptr, M, t * TM);
   idx_load_body(R, col, w);
   for (; t < ntiles;) {
@@ -242,10 +256,25 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
     adj_scatter<false>(scr, sm.rp, R, r0, col, w);
     if (has_next) idx_load_head(R, rowptr, M, tn * TM);
     f32x16 z0 = {}, z1 = {};
-    if (FIRST) {
+    [[maybe_unused]] f32x16 p0 = {}, p1 = {};
+    if (MODE == 1 || MODE == 3) {
       // H_0^T = W_0 X^T: A = W_0 planes (registers), B = X planes; node on the lane
       gemm_feat<true>(z0, z1, wf, sm);
-      if (!(S3ABL & 32)) load_wf(wf, Wp, 1);
+      if (!(S3ABL & 32)) load_wf(wf, Wp, MODE == 1 ? 1 : L + 1);
+    }
+    if (MODE == 3)  // H_0 of the closed tile: a store only, the X planes stay
+      epilogue<false, false>(sm, z0, z1, sm.bias[0], mkbuf(args.H[0], M * args.width[1] * 4),
+                             args.width[1], r0);
+    if (FOLD) {
+      // conv 1's GEMM1 on the X planes: P = X W_10^T + 1 b_10^T (needs no Â: behind the scatter)
+      // (the next weights are loaded behind conv 1's GEMM2, as in every layer: held from here
+      // they would cost 96 registers through the Â planes and GEMM2)
+      gemm_feat<false>(p0, p1, wf, sm);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        p0[i] += b10;
+        p1[i] += b10;
+      }
     }
     S3STAMP();  // 2: scatter + in_proj GEMM
     if (has_next) idx_load_body(R, col, w);
@@ -264,7 +293,7 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
 #pragma unroll
       for (int i = 0; i < 4; ++i) bst4(ba, 64 * tq + 16 * i, av[i]);
     }
-    if (FIRST)
+    if (MODE == 1)
       epilogue<false, true>(sm, z0, z1, sm.bias[0], mkbuf(args.H[0], M * args.width[1] * 4),
                             args.width[1], r0);
     S3STAMP();  // 4: in_proj epilogue
@@ -299,12 +328,9 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
     lds_barrier();
     const bool exact = sm.flag == 0;
     S3STAMP();  // 5: Â planes + B4
-    for (int l = 1; l <= L; ++l) {
+    // conv l from its P (p0 / p1) on: split, GEMM2, the next weights, epilogue
+    auto conv_tail = [&](int l) __attribute__((always_inline)) {
       const int N = args.width[l + 1];
-      // GEMM1: P = H W_l^T (A = H planes, B = W_l planes; feature on the lane)
-      f32x16 p0 = {}, p1 = {};
-      gemm_feat<false>(p0, p1, wf, sm);
-      S3STAMP();  // l: W load + GEMM1
       // the next tile's rows, a GEMM2 and an epilogue ahead of their use (vmcnt is in order:
       // they are issued after this layer's weight loads, before the next ones)
       if (l == L && has_next && !(S3ABL & 64)) load_rows(xr, bX, K0, (int)(tn * TM));
@@ -361,7 +387,7 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
       S3STAMP();  // l: GEMM2
       // the next layer's weights (or the first layer's, for the next tile): issued before the
       // epilogue's stores so that waiting for them never waits for the stores
-      if (!(S3ABL & 32)) load_wf(wf, Wp, l < L ? l + 1 : l0);
+      if (!(S3ABL & 32)) load_wf(wf, Wp, l < L ? l + 1 : w_first);
       lds_barrier();  // every read of the H planes and Â done
       S3STAMP();  // l: B5
       const Buf hb = mkbuf(args.H[l], M * N * 4);
@@ -374,6 +400,17 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
         epilogue<true, false>(sm, z0, z1, sm.bias[l], hb, N, r0);
         S3STAMP();  // L: epilogue
       }
+    };
+    // folded: conv 1's GEMM1 was taken above (peeled, so the weight registers are free from
+    // there to conv 1's GEMM2)
+    if (FOLD) conv_tail(1);
+    for (int l = FOLD ? 2 : 1; l <= L; ++l) {
+      // GEMM1: P = H W_l^T (A = H planes, B = W_l planes; feature on the lane)
+      p0 = f32x16{};
+      p1 = f32x16{};
+      gemm_feat<false>(p0, p1, wf, sm);
+      S3STAMP();  // l: W load + GEMM1
+      conv_tail(l);
     }
     t = tn;
   }
@@ -389,7 +426,7 @@ __global__ __launch_bounds__(NT, 2) void k_s3_fwd(const float* __restrict__ X, i
         fwd_tiles<false, LGNN_ACT_NONE>(lw.A, lw.C, lw.ti, X, M, K, nullptr, nullptr, nullptr,
                                         0.f, o.W[0], args.b[0], N, args.H[0], nullptr, tmask, 1);
       else
-        fwd_tiles<true, LGNN_ACT_ELU>(lw.A, lw.C, lw.ti, l == 1 && !FIRST ? X : args.H[l - 1], M,
+        fwd_tiles<true, LGNN_ACT_ELU>(lw.A, lw.C, lw.ti, l == 1 && !MODE ? X : args.H[l - 1], M,
                                       K, rowptr, col, w, 0.f, o.W[l], args.b[l], N, args.H[l],
                                       o.S[l - 1], tmask, 1);
     }
@@ -412,31 +449,64 @@ extern "C" int lgnn_s3_debug_stamps(unsigned long long* host_out) {
 hipError_t lgnn_s3_fbwd_occupancy(int* per_cu);  // stack3_bwd.hip
 
 // Workgroups of a fused stack kernel that can be resident on this device at once (occupancy
-// per CU x CU count), cached per device: which = 0 forward (k_s3_fwd<true>), 1 backward
-// (k_s3_fbwd<3, true>). A negative value is a HIP error code.
-extern "C" int lgnn_fused_grid_capacity(int which) {
-  static int cache[2][16];
-  static bool have[2][16];
+// per CU x CU count), cached per device and variant: slot 0..3 the forward k_s3_fwd<mode>, 4 the
+// backward (k_s3_fbwd<3, true>). A negative value is a HIP error code.
+static int fused_capacity(int slot) {
+  static int cache[5][16];
+  static bool have[5][16];
   int dev = 0;
-  if (which < 0 || which > 1) return LGNN_EINVAL;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -(int)hipErrorInvalidDevice;
-  if (have[which][dev]) return cache[which][dev];
+  if (have[slot][dev]) return cache[slot][dev];
   int cus = 0, per_cu = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return -(int)hipGetLastError();
-  const hipError_t e = which == 0
-      ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<true>,
-                                                     lgnn_tile::NT, 0)
-      : lgnn_s3_fbwd_occupancy(&per_cu);
+  hipError_t e;
+  switch (slot) {
+    case 0:
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<0>,
+                                                       lgnn_tile::NT, 0);
+      break;
+    case 1:
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<1>,
+                                                       lgnn_tile::NT, 0);
+      break;
+    case 2:
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<2>,
+                                                       lgnn_tile::NT, 0);
+      break;
+    case 3:
+      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<3>,
+                                                       lgnn_tile::NT, 0);
+      break;
+    default:
+      e = lgnn_s3_fbwd_occupancy(&per_cu);
+  }
   if (e != hipSuccess) return -(int)e;
-  cache[which][dev] = cus * per_cu;
-  have[which][dev] = true;
-  return cache[which][dev];
+  cache[slot][dev] = cus * per_cu;
+  have[slot][dev] = true;
+  return cache[slot][dev];
+}
+
+// which = 0: the forward — the smallest over its variants, so a grid that fits runs in every
+// mode (the launch itself checks its own variant's); 1: the backward.
+extern "C" int lgnn_fused_grid_capacity(int which) {
+  if (which < 0 || which > 1) return LGNN_EINVAL;
+  if (which == 1) return fused_capacity(4);
+  int cap = 0;
+  for (int m = 0; m < 4; ++m) {
+    const int c = fused_capacity(m);
+    if (c < 0) return c;
+    cap = m == 0 || c < cap ? c : cap;
+  }
+  return cap;
 }
 
 extern "C" size_t lgnn_weight_planes_bytes(int nl) {
-  if (nl < 1 || nl > LGNN_MAX_STACK) return 0;
-  return (size_t)nl * 3 * lgnn_s3::PLANE * sizeof(uint16_t);
+  const bool fold = nl > 0 && (nl & LGNN_PLANE_JOB_FOLD);
+  if (fold) nl &= ~LGNN_PLANE_JOB_FOLD;
+  if (nl < 1 || nl > LGNN_MAX_STACK || (fold && (nl < 2 || nl > LGNN_PLANE_JOB_MAX - 1))) return 0;
+  return (size_t)(nl + fold) * 3 * lgnn_s3::PLANE * sizeof(uint16_t) +
+         (fold ? lgnn_s3::WP * sizeof(float) : 0);
 }
 
 extern "C" int lgnn_weight_planes(int nl, const float* const* W, const int* widths,
@@ -444,7 +514,7 @@ extern "C" int lgnn_weight_planes(int nl, const float* const* W, const int* widt
   lgnn_s3::PlaneArgs a;
   const int r = lgnn_s3::plane_args(nl, W, widths, planes, planes_t, a);
   if (r != LGNN_OK) return r;
-  const int threads = nl * lgnn_s3::PLANE_ITEMS;
+  const int threads = lgnn_s3::plane_items(a);
   hipLaunchKernelGGL(lgnn_s3::k_wplanes, dim3((threads + 255) / 256), dim3(256), 0,
                      as_stream(stream), a);
   const hipError_t e = hipGetLastError();
@@ -484,8 +554,10 @@ static int stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
                         float* const* H, const int32_t* tile_open, const float* const* Wf,
                         float* const* S, int32_t* sync, void* adjt, void* stream) {
   if (M < 0 || L < 1 || L + 1 > LGNN_MAX_STACK || !planes || !b || !widths || !H || !rowptr ||
-      !col || !tile_open)
+      !col || !tile_open || has_in_proj < 0 || has_in_proj > LGNN_S3_FWD_FOLD_H0)
     return LGNN_EINVAL;
+  // folded: the fold slot sits behind the L + 1 layers' (a flagged plane job has room for 7)
+  if (has_in_proj >= LGNN_S3_FWD_FOLD && L + 1 > LGNN_PLANE_JOB_MAX - 1) return LGNN_EINVAL;
   lgnn_tile::StackArgs a = {};
   const int l0 = has_in_proj ? 0 : 1;
   if (!has_in_proj && widths[0] != d_in) return LGNN_EINVAL;
@@ -515,16 +587,27 @@ static int stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
   // open tiles behind grid barriers need every workgroup resident at once: refuse (the caller
   // then runs them in separate launches) rather than let a barrier time out
   if (sync) {
-    const int cap = lgnn_fused_grid_capacity(0);
+    const int cap = fused_capacity(has_in_proj);
     if (cap < (int)grid.x) return cap == LGNN_EINVAL ? cap : cap < 0 ? -cap : LGNN_EBUSY;
   }
   hipStream_t s = as_stream(stream);
-  if (has_in_proj)
-    hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<true>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr,
-                       col, w, L, a, planes, tile_open, o);
-  else
-    hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<false>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr,
-                       col, w, L, a, planes, tile_open, o);
+  switch (has_in_proj) {
+    case 0:
+      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<0>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr, col,
+                         w, L, a, planes, tile_open, o);
+      break;
+    case 1:
+      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<1>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr, col,
+                         w, L, a, planes, tile_open, o);
+      break;
+    case LGNN_S3_FWD_FOLD:
+      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<LGNN_S3_FWD_FOLD>, grid, dim3(lgnn_tile::NT), 0, s, X,
+                         M, rowptr, col, w, L, a, planes, tile_open, o);
+      break;
+    default:
+      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<LGNN_S3_FWD_FOLD_H0>, grid, dim3(lgnn_tile::NT), 0, s,
+                         X, M, rowptr, col, w, L, a, planes, tile_open, o);
+  }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? LGNN_OK : (int)e;
 }

@@ -133,6 +133,12 @@ HEAD_FOLD = True
 # lgnn_gcn_fold_wgrad launch per step forms dW_0, db_0 and dW_1 from the reduced sums
 # (DEFER_FOLD = False: the kernel's legacy mode, every gradient per workgroup)
 DEFER_FOLD = True
+# the fused split-3 forward (in_proj present, 1 <= L <= 2) folds in_proj into conv 1 on its closed
+# tiles: P_1 = X (W_1 W_0)^T + 1 (W_1 b_0)^T from the plane job's fold slot, made from the live
+# weights every step; no in_proj GEMM, and no H_0 of a closed tile when the deferred backward (which
+# never reads it) follows — otherwise H_0 is stored as before (FWD_FOLD = False: the unfolded
+# forward). The logits do not depend on which backward follows.
+FWD_FOLD = True
 _CAPACITY: dict = {}
 
 
@@ -186,26 +192,35 @@ def _mode_open_in_fused(mode, graph: Graph, direction: str) -> bool:
     return n > 0 and (64 % n == 0 or n % 64 == 0)
 
 
-def plane_buffers(Ws: list, transposed: bool = False, extra: int = 0):
+def plane_buffers(Ws: list, transposed: bool = False, extra: int = 0, fold: bool = False):
     """Uninitialised buffers for the bf16 three-plane images of the stack weights (split-3
     kernels): (planes [L+1, 3, 128, 128] int16, planes_t or None). planes_t is flat: the
-    transposed planes, then `extra` int16 of room (the forward's Â^T planes, bwd_planes_numel)."""
+    transposed planes, then `extra` int16 of room (the forward's Â^T planes, bwd_planes_numel).
+    fold: `planes` is flat and also holds the fold slot (W_1 W_0's planes) and the 128 floats of
+    W_1 b_0 behind the layers' slots; planes_t is the same either way."""
     nl = len(Ws)
     dev = Ws[0].device
-    planes = torch.empty(nl, 3, 128, 128, dtype=torch.int16, device=dev)
+    if fold:
+        planes = torch.empty((nl + 1) * 3 * 128 * 128 + 2 * 128, dtype=torch.int16, device=dev)
+    else:
+        planes = torch.empty(nl, 3, 128, 128, dtype=torch.int16, device=dev)
     planes_t = torch.empty(nl * 3 * 128 * 128 + extra, dtype=torch.int16, device=dev) \
         if transposed else None
     return planes, planes_t
 
 
-def plane_job(Ws: list, d_in: int, planes, planes_t) -> _lib.PlaneJob:
+def plane_job(Ws: list, d_in: int, planes, planes_t, b0=None) -> _lib.PlaneJob:
     """lgnn_plane_job: the split of Ws into `planes` / `planes_t` (lgnn_weight_planes' arguments),
-    run by the graph build's first launch (Graph.csr_planes) or by lgnn_weight_planes."""
+    run by the graph build's first launch (Graph.csr_planes) or by lgnn_weight_planes. b0
+    (in_proj's bias): the job also writes the fold slot (LGNN_PLANE_JOB_FOLD; `planes` from
+    plane_buffers(fold=True))."""
     nl = len(Ws)
-    if nl > _lib.LGNN_PLANE_JOB_MAX:
+    if nl > _lib.LGNN_PLANE_JOB_MAX - (b0 is not None):
         raise _lib.LgnnError("plane job: too many layers")
     job = _lib.PlaneJob()
-    job.nl = nl
+    job.nl = nl | (_lib.LGNN_PLANE_JOB_FOLD if b0 is not None else 0)
+    if b0 is not None:
+        job.W[nl] = b0.data_ptr()
     widths = [d_in] + [W.size(0) for W in Ws]
     for i, v in enumerate(widths):
         job.widths[i] = v
@@ -213,13 +228,15 @@ def plane_job(Ws: list, d_in: int, planes, planes_t) -> _lib.PlaneJob:
         job.W[i] = W.data_ptr()
     job.planes = planes.data_ptr()
     job.planes_t = planes_t.data_ptr() if planes_t is not None else None
-    job._keep = (Ws, planes, planes_t)  # the pointers' owners live as long as the job
+    job._keep = (Ws, planes, planes_t, b0)  # the pointers' owners live as long as the job
     return job
 
 
 def run_plane_job(job: _lib.PlaneJob, dev) -> None:
     """The split of `job` as its own launch (lgnn_weight_planes)."""
-    _lib.call("lgnn_weight_planes", job.nl, job.W[:job.nl], job.widths[:job.nl + 1], job.planes,
+    layers = job.nl & ~_lib.LGNN_PLANE_JOB_FOLD
+    nw = layers + (1 if job.nl != layers else 0)  # folded: b_0 behind the weights
+    _lib.call("lgnn_weight_planes", job.nl, job.W[:nw], job.widths[:layers + 1], job.planes,
               job.planes_t, _s(dev))
 
 
@@ -247,6 +264,13 @@ def bwd_planes_numel(L: int, M) -> int:
     return (L + 1) * 3 * 128 * 128 + (adjt_numel(M) if _s3f(L) and ADJT else 0)
 
 
+def _defers_fold(L: int, s3: bool) -> bool:
+    """The fused backward of an L-conv stack runs in its deferred mode (it never reads H_0).
+    stack_bwd's `defer` and the forward's choice to leave H_0's closed rows unwritten
+    (gcn_stack_fwd) both come from here."""
+    return DEFER_FOLD and s3 and _s3f(L) and L <= 2
+
+
 def _s3f(L: int) -> bool:
     """The fused split-3 backward takes L <= 2 convs in one launch, and L = 3 with the in_proj
     weight gradient outside it (the kernel writes dZ_0; stack_bwd runs the GEMM) when its
@@ -271,7 +295,8 @@ def stack_fwd(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: str = "gc
 
 
 def stack_fwd_planes(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: str = "gcn",
-                     keep_planes: bool = False, adjt_after_planes: bool = False):
+                     keep_planes: bool = False, adjt_after_planes: bool = False,
+                     fold: bool = False, keep_h0: bool = True):
     """in_proj + L x ELU(GCNConv) forward, every width <= 128: returns ([H_0..H_L],
     [S_1..S_L], planes_t, adjt_t). Tiles no edge leaves run fused through every layer
     (lgnn_gcn_stack_fwd); the rest (graphs straddling 64-node tiles) layer by layer
@@ -281,19 +306,25 @@ def stack_fwd_planes(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: st
     keep_planes (split-3 only): planes_t = the transposed weight planes for the split-3 backward,
     adjt_t = the Â^T tiles for its single-launch form (None when ADJT is off or L > 3) — or, with
     adjt_after_planes, those tiles in room after the planes inside planes_t (one buffer: the
-    compiled lgnn::gcn_stack op returns it as an output of its own) and adjt_t None."""
+    compiled lgnn::gcn_stack op returns it as an output of its own) and adjt_t None.
+    fold (split-3 only, L >= 1): the closed tiles take in_proj folded into conv 1
+    (LGNN_S3_FWD_FOLD_H0); with keep_h0 False (LGNN_S3_FWD_FOLD) the closed tiles' rows of H_0 are
+    left unwritten. H_1..H_L are the same bits either way."""
     M = x.size(0)
     L = len(Ws) - 1
     dev = x.device
     s3 = MFMA_MODE == "s3" and L >= 1
+    if fold and not s3:
+        raise _lib.LgnnError("stack_fwd_planes: fold needs the split-3 forward")
+    mode = 1 if not fold else _lib.LGNN_S3_FWD_FOLD_H0 if keep_h0 else _lib.LGNN_S3_FWD_FOLD
     if s3:
         # the transposed planes (the split-3 backward's dH = G W_l operand) come from the same
         # split when the caller keeps them; the split rides the graph build when this forward
         # builds the graph
         want_adjt = keep_planes and _s3f(L) and ADJT
         extra = adjt_numel(M) if want_adjt and adjt_after_planes else 0
-        planes, planes_t = plane_buffers(Ws, transposed=keep_planes, extra=extra)
-        job = plane_job(Ws, x.size(1), planes, planes_t)
+        planes, planes_t = plane_buffers(Ws, transposed=keep_planes, extra=extra, fold=fold)
+        job = plane_job(Ws, x.size(1), planes, planes_t, bs[0] if fold else None)
         csr, split_done = graph.csr_planes(kind, job)
         if not split_done:
             run_plane_job(job, dev)
@@ -312,10 +343,10 @@ def stack_fwd_planes(x: torch.Tensor, graph: Graph, Ws: list, bs: list, kind: st
     widths = [W.size(0) for W in Ws]
     if s3:
         if _open_in_fused(OPEN_IN_FUSED, graph, "fwd"):  # open tiles in the same launch
-            _lib.call("lgnn_gcn_stack_fwd_s3_all", x, M, x.size(1), 1, csr.rowptr, csr.col,
+            _lib.call("lgnn_gcn_stack_fwd_s3_all", x, M, x.size(1), mode, csr.rowptr, csr.col,
                       csr.w, L, planes, Ws, bs, widths, hs, ss, open_, adjt, _s(dev))
             return hs, ss, planes_t, adjt_t
-        _lib.call("lgnn_gcn_stack_fwd_s3", x, M, x.size(1), 1, csr.rowptr, csr.col, csr.w, L,
+        _lib.call("lgnn_gcn_stack_fwd_s3", x, M, x.size(1), mode, csr.rowptr, csr.col, csr.w, L,
                   planes, bs, widths, hs, open_, adjt, _s(dev))
     else:
         _lib.call("lgnn_gcn_stack_fwd", x, M, x.size(1), 1, csr.rowptr, csr.col, csr.w, L, Ws,
@@ -370,7 +401,7 @@ def stack_bwd(dp: torch.Tensor | None, x: torch.Tensor, graph: Graph, mean: bool
     _lib.check(0 if P > 0 else P, "lgnn_gcn_stack_bwd_partials")
     widths = [x.size(1)] + [W.size(0) for W in Ws]
     per = [widths[l + 1] * widths[l] + widths[l + 1] for l in range(L + 1)]
-    defer = DEFER_FOLD and s3f and L <= 2 and b0 is not None
+    defer = _defers_fold(L, s3) and b0 is not None
     if defer:  # the T [w2][d_in] / g [w2] slabs ride behind the layers'
         per.append(widths[2] * widths[0] + widths[2])
         hs = [None] + list(hs[1:])
@@ -1140,8 +1171,15 @@ def gcn_plan(shapes: list, L: int, lazy_ok: bool = False) -> GcnPlan:
 # hs = [H_0..H_L]; ss = [S_1..S_L] (H_{l-1} itself where plan.saved_s[l] is False); params =
 # [W_in, b_in, (W_l, b_l) * L, W_out, b_out]; planes_t (plan.keeps_planes, else None): the
 # transposed weight planes (+ Â^T room); adjt: the forward's Â^T tiles when they have a buffer
-# of their own, else None
-GcnSaved = namedtuple("GcnSaved", "x pooled hs ss params planes_t adjt graph mean L plan")
+# of their own, else None; h0_valid: hs[0] holds every row (False: the folded forward left its
+# closed tiles' rows unwritten, for the deferred backward)
+GcnSaved = namedtuple("GcnSaved", "x pooled hs ss params planes_t adjt graph mean L plan h0_valid",
+                      defaults=(True,))
+
+
+def _bwd_defers(plan: GcnPlan, L: int, want_dx: bool) -> bool:
+    """The backward gcn_stack_bwd will run is the deferred fused one."""
+    return plan.fused_bwd and not want_dx and _defers_fold(L, plan.keeps_planes)
 
 
 def gcn_stack_fwd(x, graph, mean, L, params, want_dx: bool, adjt_after_planes: bool = False):
@@ -1154,10 +1192,14 @@ def gcn_stack_fwd(x, graph, mean, L, params, want_dx: bool, adjt_after_planes: b
     plan = gcn_plan([tuple(W.shape) for W in Ws], L,
                     lazy_ok=isinstance(graph, Graph) and not want_dx)
     planes_t = adjt = None
+    h0_valid = True
     if plan.fused:  # builds the graph itself (with the weight-plane split riding along)
+        fold = FWD_FOLD and MFMA_MODE == "s3" and 1 <= L <= 2
+        # H_0's closed rows are dropped only when the backward that follows never reads them
+        h0_valid = not (fold and _bwd_defers(plan, L, want_dx))
         hs, ss, planes_t, adjt = stack_fwd_planes(
             x, graph, Ws, [params[2 * l + 1] for l in range(L + 1)], plan.kind,
-            plan.keeps_planes, adjt_after_planes)
+            plan.keeps_planes, adjt_after_planes, fold=fold, keep_h0=h0_valid)
     else:
         csr = graph.csr(plan.kind)
         hs = [linear_fwd(x, W_in, b_in, _lib.LGNN_ACT_NONE)]
@@ -1172,7 +1214,8 @@ def gcn_stack_fwd(x, graph, mean, L, params, want_dx: bool, adjt_after_planes: b
             ss.append(s_)
     W_out, b_out = params[2 + 2 * L], params[3 + 2 * L]
     pooled, logits = pool_head_fwd(hs[-1], graph, mean, W_out, b_out)
-    return logits, GcnSaved(x, pooled, hs, ss, params, planes_t, adjt, graph, mean, L, plan)
+    return logits, GcnSaved(x, pooled, hs, ss, params, planes_t, adjt, graph, mean, L, plan,
+                            h0_valid)
 
 
 def gcn_fused_head(sv: GcnSaved, want_dx: bool) -> bool:
@@ -1193,6 +1236,10 @@ def gcn_stack_bwd(sv: GcnSaved, dlogits, want_dx: bool, ce=None):
     dlogits = _f32c(dlogits) if dlogits is not None else None
     grads = [None] * len(params)
     red: list = []
+    if not sv.h0_valid and not _bwd_defers(sv.plan, L, want_dx):
+        # the switches changed since the forward: this backward reads H_0, which the folded
+        # forward did not write for the closed tiles
+        hs = [linear_fwd(x, params[0], params[1], _lib.LGNN_ACT_NONE)] + list(hs[1:])
     if sv.plan.fused_bwd and not want_dx:
         Ws = [params[2 * l] for l in range(L + 1)]
         if head_in_stack_bwd(graph, L, W_out.size(0), sv.planes_t is not None):
