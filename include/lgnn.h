@@ -1348,6 +1348,68 @@ int lgnn_collate(const int64_t* ids, int64_t num_sel, const int64_t* src_ptr,
                  int64_t* out_batch, int64_t* out_ptr, int64_t out_capacity, int32_t* err,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SIFT nodes for a batch of images of one size. Replaces: cv2.SIFT_create(nfeatures,
+ * contrastThreshold = 0, sigma).detectAndCompute of the reference's SiftExtractor
+ * (src/lesion_gnn/datasets/nodes/sift.py:50-52): OpenCV's algorithm with nOctaveLayers = 3 and
+ * edgeThreshold = 10, restated (parity with OpenCV itself is not pinned). The
+ * entries are additions: every earlier signature is unchanged, so the ABI version stays.
+ *   Sizes: 1 <= batch <= 65535, height, width >= 2, batch * 24 * height * width < 2^31; sigma > 0
+ *   with every blur radius <= LGNN_SIFT_MAX_RADIUS (sigma up to about 1.9). Anything else is
+ *   LGNN_EINVAL before any launch, as are a NULL required pointer and a capacity or workspace
+ *   that is too small.
+ *   The pyramid: the image is doubled, so octave o is (2 * height >> o) x (2 * width >> o);
+ *   lgnn_sift_num_octaves of them are built (those whose smaller side exceeds 10; 0 for sizes the
+ *   entries refuse). The Gaussian buffer holds, octave after octave, [batch][6][h][w] fp32, the
+ *   DoG buffer [batch][5][h][w]: lgnn_sift_pyramid_floats(batch, height, width) floats and 5/6 of
+ *   that.
+ * lgnn_sift_pyramid: image [batch, height, width, channels] uint8, channels 1 or 3 -> gray
+ *   [batch, height, width] uint8 ((c0 * 1868 + c1 * 9617 + c2 * 4899 + 8192) >> 14: the
+ *   reference's RGB array read as BGR) and both buffers. 1 + 6 launches per octave.
+ * lgnn_sift_count: counts [rows] and row_ptr [rows + 1] int32, rows = lgnn_sift_rows(batch,
+ *   height, width): one row per (image, octave, layer 1..3, row); row_ptr is the exclusive scan
+ *   of the rows' 26-neighbour extrema at least 5 pixels from every edge, row_ptr[rows] their
+ *   total (the caller reads it to size cand). Two launches.
+ * lgnn_sift_candidates: cand [capacity, 5] int32 (image, octave, layer, row, column) in that
+ *   order; nothing is written at or beyond row `capacity`. One launch.
+ * lgnn_sift_keypoints: refinement (adjustLocalExtrema), orientation peaks, removal of keypoints
+ *   equal in (pt, size, angle) to an earlier one, and the cut at the num_keypoints-th largest
+ *   response (ties kept), per image; float64 on the fp32 levels. cand must be ordered by image;
+ *   entries outside the pyramid are skipped. node_ptr [batch + 1] int64, written: the exclusive
+ *   scan of the keypoints kept per image; the caller reads it to size the outputs. The rest
+ *   stays in the workspace (lgnn_sift_keypoints_workspace_bytes(batch, num_candidates); 0 for
+ *   counts the entry refuses) for lgnn_sift_gather. num_keypoints >= 1. Nine launches.
+ * lgnn_sift_gather: the same workspace -> kf [total_nodes, 5] fp32 (x, y, size, angle, response;
+ *   pt and size halved for the doubled image) and ki [total_nodes, 3] int32 (image, octave,
+ *   layer), image by image, by response descending, then candidate order. One launch.
+ * lgnn_sift_descriptors: kf, ki as above (any keypoints; entries outside the pyramid give a
+ *   zero row) -> x [num_nodes, 128] fp32, integers in 0..255 (calcSIFTDescriptor), one wave per
+ *   keypoint. One launch.
+ * No float atomics: two calls give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_SIFT_MAX_OCTAVES 16
+#define LGNN_SIFT_MAX_RADIUS 16
+#define LGNN_SIFT_MAX_PEAKS 18
+int lgnn_sift_num_octaves(int height, int width);
+size_t lgnn_sift_pyramid_floats(int batch, int height, int width);
+int lgnn_sift_pyramid(const uint8_t* image, int batch, int height, int width, int channels,
+                      double sigma, uint8_t* gray, float* gauss, size_t gauss_floats, float* dog,
+                      size_t dog_floats, void* stream);
+size_t lgnn_sift_rows(int batch, int height, int width);
+int lgnn_sift_count(const float* dog, int batch, int height, int width, int32_t* counts,
+                    int32_t* row_ptr, void* stream);
+int lgnn_sift_candidates(const float* dog, int batch, int height, int width,
+                         const int32_t* row_ptr, int32_t* cand, int capacity, void* stream);
+size_t lgnn_sift_keypoints_workspace_bytes(int batch, int num_candidates);
+int lgnn_sift_keypoints(const float* gauss, const float* dog, int batch, int height, int width,
+                        double sigma, const int32_t* cand, int num_candidates, int num_keypoints,
+                        int64_t* node_ptr, void* workspace, size_t workspace_bytes, void* stream);
+int lgnn_sift_gather(int batch, int num_candidates, const int64_t* node_ptr, int total_nodes,
+                     float* kf, int32_t* ki, void* workspace, size_t workspace_bytes,
+                     void* stream);
+int lgnn_sift_descriptors(const float* gauss, int batch, int height, int width, const float* kf,
+                          const int32_t* ki, int num_nodes, float* x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

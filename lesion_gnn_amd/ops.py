@@ -2514,6 +2514,159 @@ def collate(store, ids, validate: bool = False):
 
 
 # ----------------------------------------------------------------------------------------------
+# SIFT nodes (sift.hip): scale space, candidates, keypoints, descriptors for a batch of images
+# ----------------------------------------------------------------------------------------------
+
+
+def sift_octave_dims(height: int, width: int) -> list[tuple[int, int]]:
+    """The (h, w) of every octave lgnn_sift_pyramid builds for (height, width) images: the
+    doubled image, halved per octave, while the smaller side exceeds 10."""
+    n = _lib.load().lgnn_sift_num_octaves(int(height), int(width))
+    return [((2 * height) >> o, (2 * width) >> o) for o in range(n)]
+
+
+class SiftPyramid(NamedTuple):
+    """The scale space of B images of one size as the kernels hold it: gray (B, H, W) uint8 (or
+    None), the Gaussian levels octave after octave as one flat fp32 buffer of (B, 6, h, w) blocks,
+    the DoG levels likewise as (B, 5, h, w). `gauss` / `dog` are the per-octave views."""
+
+    gray: torch.Tensor | None
+    gauss_flat: torch.Tensor
+    dog_flat: torch.Tensor
+    shape: tuple  # (B, H, W)
+
+    def _views(self, flat: torch.Tensor, levels: int) -> list[torch.Tensor]:
+        B, H, W = self.shape
+        out, at = [], 0
+        for h, w in sift_octave_dims(H, W):
+            n = B * levels * h * w
+            out.append(flat[at:at + n].view(B, levels, h, w))
+            at += n
+        return out
+
+    @property
+    def gauss(self) -> list[torch.Tensor]:
+        return self._views(self.gauss_flat, 6)
+
+    @property
+    def dog(self) -> list[torch.Tensor]:
+        return self._views(self.dog_flat, 5)
+
+    @classmethod
+    def from_levels(cls, gauss, dog, gray: torch.Tensor | None = None) -> "SiftPyramid":
+        """From per-octave tensors (B, 6, h, w) and (B, 5, h, w) (either list may be None: the
+        stage that is run does not read it), e.g. an oracle's levels."""
+        some = gauss if gauss is not None else dog
+        _lib.require_gpu(*some)
+        B, _, h, w = some[0].shape
+        if h % 2 or w % 2:
+            raise ValueError("octave 0 is the doubled image: its sides are even")
+        shape = (B, h // 2, w // 2)
+        dims = sift_octave_dims(*shape[1:])
+
+        def pack(levels, count):
+            if levels is None:
+                return torch.empty(0, dtype=torch.float32, device=some[0].device)
+            if [tuple(t.shape) for t in levels] != [(B, count, a, b) for a, b in dims]:
+                raise ValueError(f"expected the octaves {[(B, count, a, b) for a, b in dims]}")
+            return torch.cat([_f32c(t).reshape(-1) for t in levels])
+
+        return cls(gray, pack(gauss, 6), pack(dog, 5), shape)
+
+
+def sift_pyramid(images: torch.Tensor, sigma: float) -> SiftPyramid:
+    """images (B, H, W, 3) or (B, H, W) uint8 -> the gray images (the reference's RGB array read
+    as BGR: red gets the 0.114 weight) and the Gaussian and DoG levels of every octave, fp32
+    (lgnn_sift_pyramid). 1 + 6 launches per octave whatever B is, no host synchronisation."""
+    if images.dtype != torch.uint8 or images.dim() not in (3, 4) or \
+            (images.dim() == 4 and images.size(3) != 3):
+        raise ValueError("images must be a (B, H, W, 3) or (B, H, W) uint8 tensor")
+    _lib.require_gpu(images)
+    img = images.contiguous()
+    B, H, W = img.shape[:3]
+    dev = img.device
+    if B < 1 or H < 2 or W < 2:
+        raise ValueError("sift_pyramid takes at least one image of at least 2 x 2 pixels")
+    n = _lib.load().lgnn_sift_pyramid_floats(B, H, W)
+    gray = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    gauss = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    dog = torch.empty(max(n // 6 * 5, 1), dtype=torch.float32, device=dev)
+    _lib.call("lgnn_sift_pyramid", img, B, H, W, 3 if img.dim() == 4 else 1, float(sigma), gray,
+              gauss, n, dog, n // 6 * 5, _s(dev))
+    return SiftPyramid(gray, gauss[:n], dog[:n // 6 * 5], (B, H, W))
+
+
+def sift_candidates(pyramid: SiftPyramid) -> torch.Tensor:
+    """The 26-neighbour extrema of DoG layers 1..3 at least 5 pixels from every edge -> cand
+    (n, 5) int32 (image, octave, layer, row, column), in that order (lgnn_sift_count,
+    lgnn_sift_candidates). Three launches and one host read: the total, which sizes cand."""
+    B, H, W = pyramid.shape
+    dog = pyramid.dog_flat
+    _lib.require_gpu(dog)
+    dev = dog.device
+    rows = _lib.load().lgnn_sift_rows(B, H, W)
+    counts = torch.empty(max(rows, 1), dtype=torch.int32, device=dev)
+    row_ptr = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_sift_count", dog if rows else None, B, H, W, counts, row_ptr, _s(dev))
+    n = int(row_ptr[rows].item())
+    cand = torch.empty(max(n, 1), 5, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_sift_candidates", dog if rows else None, B, H, W, row_ptr, cand, n, _s(dev))
+    return cand[:n]
+
+
+def sift_keypoints(pyramid: SiftPyramid, cand: torch.Tensor, sigma: float, num_keypoints: int
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """cand (n, 5) int32 as `sift_candidates` gives them -> (kf (m, 5) fp32: x, y, size, angle,
+    response, pt and size halved for the doubled image; ki (m, 3) int32: image, octave, layer;
+    node_ptr (B + 1) int64 on the device; its host copy): refinement, orientation peaks,
+    duplicate removal and the cut at the num_keypoints-th largest response (ties kept), per image
+    by response descending, then candidate order (lgnn_sift_keypoints, lgnn_sift_gather). Ten
+    launches and one host read: node_ptr, which sizes the outputs."""
+    B, H, W = pyramid.shape
+    _lib.require_gpu(pyramid.gauss_flat, pyramid.dog_flat, cand)
+    if cand.dim() != 2 or cand.size(1) != 5 or cand.dtype != torch.int32:
+        raise ValueError("cand must be a (n, 5) int32 tensor")
+    if int(num_keypoints) < 1:
+        raise ValueError("num_keypoints must be at least 1")
+    c = cand.contiguous()
+    n = c.size(0)
+    dev = c.device
+    nws = _lib.load().lgnn_sift_keypoints_workspace_bytes(B, n)
+    if nws == 0:
+        raise ValueError(f"sift_keypoints: {n} candidates are more than the entry takes")
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    node_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    on = bool(n)
+    _lib.call("lgnn_sift_keypoints", pyramid.gauss_flat if on else None,
+              pyramid.dog_flat if on else None, B, H, W, float(sigma), c if on else None, n,
+              int(num_keypoints), node_ptr, ws, nws, _s(dev))
+    ptr_host = node_ptr.cpu()
+    m = int(ptr_host[-1])
+    kf = torch.empty(max(m, 1), 5, dtype=torch.float32, device=dev)
+    ki = torch.empty(max(m, 1), 3, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_sift_gather", B, n, node_ptr, m, kf, ki, ws, nws, _s(dev))
+    return kf[:m], ki[:m], node_ptr, ptr_host
+
+
+def sift_descriptors(pyramid: SiftPyramid, kf: torch.Tensor, ki: torch.Tensor) -> torch.Tensor:
+    """kf (m, 5) fp32 and ki (m, 3) int32 as `sift_keypoints` gives them -> (m, 128) fp32, the
+    4 x 4 x 8 descriptors as integers in 0..255, read from each keypoint's Gaussian level
+    (lgnn_sift_descriptors). One launch, no host synchronisation."""
+    B, H, W = pyramid.shape
+    _lib.require_gpu(pyramid.gauss_flat, kf, ki)
+    if kf.dim() != 2 or kf.size(1) != 5 or ki.dim() != 2 or ki.size(1) != 3 or \
+            ki.dtype != torch.int32 or kf.size(0) != ki.size(0):
+        raise ValueError("kf must be (m, 5) fp32 and ki (m, 3) int32")
+    f, k = _f32c(kf), ki.contiguous()
+    m = f.size(0)
+    dev = f.device
+    x = torch.empty(max(m, 1), 128, dtype=torch.float32, device=dev)
+    if m:
+        _lib.call("lgnn_sift_descriptors", pyramid.gauss_flat, B, H, W, f, k, m, x, _s(dev))
+    return x[:m]
+
+
+# ----------------------------------------------------------------------------------------------
 # Set attention (setattn.hip): segmented multi-head attention over ragged sets, the residual +
 # activation + LayerNorm of PyG's MultiheadAttentionBlock, the set readout
 # ----------------------------------------------------------------------------------------------
