@@ -22,43 +22,18 @@
 #include <algorithm>
 
 #include "common.h"
-#include "tile_util.h"
+#include "s3_util.h"
 
 namespace lgnn_bf {
 using namespace lgnn_tile;
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int BK = 64;          // k per chunk
-constexpr int ROWB = BK * 2;    // bytes per image row
-constexpr int OOB = 0x7ff00000;  // buffer offset past every range: the load returns 0
+using namespace lgnn_s3;  // the bf16 A image (BK, ROWB, swz, lds16), opaque, ldb32, OOB
 
 __device__ __forceinline__ uint32_t pk2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{a, b}), bf16x2));
 }
-// 16-B chunk XOR-swizzled by (row >> 1) & 7: the 16 rows of a ds_read_b128 lane group land in
-// 16 distinct 16-B bank slots (s3gemm.hip swz)
-__device__ __forceinline__ int swz(int row, int chunk) {
-  return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-__device__ __forceinline__ u32x4 lds16(const unsigned char* p) {
-  return *reinterpret_cast<const u32x4*>(p);
-}
 __device__ __forceinline__ f32x16 mfma_bf(u32x4 a, u32x4 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
                                                  __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// a value through an empty asm: a select feeding a buffer offset stays a v_cndmask instead of being
-// sunk into two branch-guarded loads (whose join makes the wait-count pass drain to vmcnt(0))
-__device__ __forceinline__ int opaque(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ uint32_t ldb32(Buf b, int off) {
-  return __builtin_amdgcn_raw_buffer_load_b32(b, off, 0, 0);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include <climits>
 
 #include "ccl.h"
+#include "wg.h"
 
 namespace lgnn_cclk {
 
@@ -189,16 +190,6 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// sum of v over the workgroup (every thread gets it); kThreads threads
-__device__ __forceinline__ int block_sum(int v, int32_t* wsum) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-  for (int w = 0; w < kWaves; ++w) s += wsum[w];
-  return s;
-}
-
 __global__ void __launch_bounds__(kThreads)
     k_ccl_compress(int32_t* parent, int64_t hw, int nbi, int32_t* __restrict__ blockcount) {
   __shared__ int32_t wsum[kWaves];
@@ -217,7 +208,7 @@ __global__ void __launch_bounds__(kThreads)
     if (r != q) __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     c += r == (int32_t)p;
   }
-  const int s = block_sum(c, wsum);
+  const int s = block_sum<kThreads>(c, wsum);
   if (threadIdx.x == 0) blockcount[blockIdx.x] = s;
 }
 
@@ -225,29 +216,14 @@ __global__ void __launch_bounds__(kScanThreads)
     k_ccl_scan(int32_t* blockcount, int nb, int nbi, int B, int32_t* __restrict__ num_labels,
                int64_t* __restrict__ node_ptr) {
   __shared__ int32_t wsum[kScanThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int carry = 0;
   for (int base = 0; base < nb; base += kScanThreads) {
     const int i = base + threadIdx.x;
-    const int v = i < nb ? blockcount[i] : 0;
-    int s = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(s, o, 64);
-      if (lane >= o) s += t;
-    }
-    if (lane == 63) wsum[wave] = s;
-    __syncthreads();
-    int woff = 0, total = 0;
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-      if (w < wave) woff += wsum[w];
-      total += wsum[w];
-    }
-    if (i < nb) blockcount[i] = carry + woff + s - v;
-    carry += total;
-    __syncthreads();
+    const int at = block_exclusive_scan<kScanThreads>(i < nb ? blockcount[i] : 0, carry, wsum);
+    if (i < nb) blockcount[i] = at;
   }
-  // per image: its roots are the difference of the offsets of its first block and the next
-  // image's (the loop ended on a barrier, so every thread's offsets are written)
+  __syncthreads();  // the offsets below were written by other threads
+  // per image: its roots are the difference of the offsets of its first block and the next image's
   for (int b = threadIdx.x; b < B; b += kScanThreads) {
     const int first = blockcount[b * nbi];
     const int next = b + 1 < B ? blockcount[(b + 1) * nbi] : carry;
@@ -272,11 +248,7 @@ __global__ void __launch_bounds__(kThreads)
     root[j] = local + j < hw && parent[p] == (int32_t)p;
     c += root[j];
   }
-  int s = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(s, o, 64);
-    if (lane >= o) s += t;
-  }
+  const int s = wave_inclusive_scan(c);
   if (lane == 63) wsum[wave] = s;
   __syncthreads();
   int r = blockoff[blockIdx.x] - blockoff[b * nbi] + s - c + 1;  // the rank restarts per image
@@ -410,7 +382,7 @@ __global__ void __launch_bounds__(kThreads)
     atomicAdd(sums + 2 * (int64_t)i, b_sx[i]);
     atomicAdd(sums + 2 * (int64_t)i + 1, b_sy[i]);
   }
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(err, bad);
 }
 

@@ -17,6 +17,7 @@
 //              divides by the count (mean). Deterministic: every float sum is in a fixed order
 //              except within one wave's LDS add instruction, whose lane order the hardware fixes.
 #include "common.h"
+#include "wg.h"
 
 namespace lgnn_ccpool {
 
@@ -54,7 +55,7 @@ __global__ void __launch_bounds__(kThreads)
   __syncthreads();
   for (int i = threadIdx.x; i < nseg; i += kThreads)
     if (hist[i]) atomicAdd(&count[i], hist[i]);
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(err, bad);
 }
 

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "wg.h"
 
 namespace lgnn_ccresample {
 
@@ -92,7 +93,7 @@ __global__ void __launch_bounds__(kThreads)
   __syncthreads();
   for (int i = threadIdx.x; i < r.n; i += kThreads)
     if (hist[i]) atomicAdd(&count[r.base + i], hist[i]);
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+  bad = wave_sum(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(err, bad);
   if (taps)  // rows first, then columns
     for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < (int64_t)H + W;

@@ -24,6 +24,7 @@
 // the row count is read on the device (out_ptr[num_sel]), and workgroups past it return at once.
 // The last workgroups of the grid do the per-row outputs (out_batch, out_pos), kRows rows each.
 #include "common.h"
+#include "wg.h"
 
 namespace {
 
@@ -54,16 +55,6 @@ __global__ __launch_bounds__(kT) void k_collate_sizes(
   out_y[b] = ok ? y[id] : -1;
 }
 
-__device__ __forceinline__ int64_t wave_inclusive_scan(int64_t v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int64_t o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
 // One workgroup: out_ptr from the sizes to their exclusive scan, delta from the first source
 // row to the row shift, in tiles of kScanT graphs (thread t owns graph tile + t: coalesced, and
 // no thread reads what another wrote), the total and err.
@@ -71,31 +62,19 @@ __global__ __launch_bounds__(kScanT) void k_collate_scan(
     int64_t num_sel, int64_t* __restrict__ out_ptr, int64_t* __restrict__ delta,
     int64_t capacity, int32_t* __restrict__ err) {
   __shared__ int64_t s_wave[kScanT / 64];
-  const int t = threadIdx.x, wave = t >> 6;
+  const int t = threadIdx.x;
   int64_t carry = 0, bad = 0;
   int64_t next = t < num_sel ? out_ptr[t] : 0;
   for (int64_t tile = 0; tile < num_sel; tile += kScanT) {
     const int64_t b = tile + t;
     const int64_t raw = next;
     next = b + kScanT < num_sel ? out_ptr[b + kScanT] : 0;  // in flight during this tile's scan
-    const int64_t n = raw > 0 ? raw : 0;
-    const int64_t incl = wave_inclusive_scan(n);
-    if ((t & 63) == 63) s_wave[wave] = incl;
     bad += __syncthreads_count(raw < 0);
-    int64_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kScanT / 64; ++w) {
-      const int64_t v = s_wave[w];
-      before += w < wave ? v : 0;
-      all += v;
-    }
+    const int64_t at = block_exclusive_scan<kScanT>(raw > 0 ? raw : (int64_t)0, carry, s_wave);
     if (b < num_sel) {
-      const int64_t at = carry + before + incl - n;
       out_ptr[b] = at;
       delta[b] -= at;
     }
-    carry += all;
-    __syncthreads();  // s_wave is rewritten by the next tile
   }
   if (t == 0) {
     out_ptr[num_sel] = carry;

@@ -13,6 +13,7 @@
 // visited in CSR order (= PyG's edge order; the self loop is last), so sums follow PyG's
 // scatter_add_ order.
 #include "common.h"
+#include "tile_util.h"
 
 namespace {
 
@@ -48,12 +49,9 @@ __device__ __forceinline__ float opaque(float v) {
 // Raw buffer access (SGPR descriptor + 32-bit byte offset): one VGPR per gathered address instead
 // of two, which is what bounds these gather kernels' registers (8 source rows in flight). Every
 // array addressed this way is < 4 GiB (checked on the host, bytes_ok).
-typedef __amdgpu_buffer_rsrc_t Buf;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ Buf mkbuf(const void* p, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)(uint32_t)bytes,
-                                           0x00020000);
-}
+using lgnn_tile::Buf;
+using lgnn_tile::mkbuf;
+using lgnn_tile::u32x4;
 __device__ __forceinline__ f32x4 bld4(Buf r, uint32_t off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }

@@ -16,60 +16,33 @@
 // Each thread keeps its best KMAX (k rounded up to a power of two) in registers as a sorted
 // list; candidates arrive in index order, so strict comparisons keep ties in index order.
 #include "common.h"
+#include "geom.h"
+#include "wg.h"
 
 namespace {
 
 constexpr int QT = 256;      // queries (threads) per block
 constexpr int CHUNK = 1024;  // candidates staged per round
 
-__device__ __forceinline__ double sqd(const double* a, const double* b, int D) {
-  // Plain operators in a contract(off) scope: each product and sum rounds on its own. (HIP's
-  // __dmul_rn / __dadd_rn carry their header's `contract` flag and still fuse into an FMA
-  // under the default -ffp-contract=fast.)
-#pragma clang fp contract(off)
-  const double dx = a[0] - b[0], dy = a[1] - b[1];
-  double s = dx * dx + dy * dy;
-  if (D == 3) {
-    const double dz = a[2] - b[2];
-    s = s + dz * dz;
-  }
-  return s;
-}
-
 // eoff[g] = first edge of graph g (exclusive scan of n_g * kk_g), eoff[B] = total. One block,
-// each thread a contiguous range of graphs (fixed order).
-__global__ __launch_bounds__(1024) void k_knn_offsets(const int32_t* __restrict__ ptr, int64_t B,
-                                                      int k, int loop,
-                                                      int64_t* __restrict__ eoff) {
-  __shared__ int64_t part[1024];
-  const int t = threadIdx.x;
-  const int64_t per = (B + 1023) / 1024;
-  const int64_t g0 = t * per, g1 = g0 + per < B ? g0 + per : B;
+// tiles of kScanTile graphs.
+__global__ __launch_bounds__(kScanTile) void k_knn_offsets(const int32_t* __restrict__ ptr,
+                                                           int64_t B, int k, int loop,
+                                                           int64_t* __restrict__ eoff) {
+  __shared__ int64_t s_wave[kScanTile / 64];
   auto edges = [&](int64_t g) -> int64_t {
     const int64_t n = ptr[g + 1] - ptr[g];
     int64_t kk = loop ? (k < n ? k : n) : ((k + 1 < n ? k + 1 : n) - 1);
     if (kk < 0) kk = 0;
     return n * kk;
   };
-  int64_t s = 0;
-  for (int64_t g = g0; g < g1; ++g) s += edges(g);
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int64_t run = 0;
-    for (int i = 0; i < 1024; ++i) {
-      const int64_t v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    eoff[B] = run;
+  int64_t carry = 0;
+  for (int64_t tile = 0; tile < B; tile += kScanTile) {
+    const int64_t g = tile + threadIdx.x;
+    const int64_t at = block_exclusive_scan<kScanTile>(g < B ? edges(g) : 0, carry, s_wave);
+    if (g < B) eoff[g] = at;
   }
-  __syncthreads();
-  int64_t run = part[t];
-  for (int64_t g = g0; g < g1; ++g) {
-    eoff[g] = run;
-    run += edges(g);
-  }
+  if (threadIdx.x == 0) eoff[B] = carry;
 }
 
 template <int KMAX, int D>
@@ -175,7 +148,7 @@ extern "C" int lgnn_knn_graph(const double* pos, int64_t N, int dims, const int6
   if (N == 0 || B == 0) return LGNN_OK;
   hipStream_t s = as_stream(stream);
   int64_t* eoff = static_cast<int64_t*>(workspace);
-  hipLaunchKernelGGL(k_knn_offsets, dim3(1), dim3(1024), 0, s, ptr, B, k, loop, eoff);
+  hipLaunchKernelGGL(k_knn_offsets, dim3(1), dim3(kScanTile), 0, s, ptr, B, k, loop, eoff);
   LGNN_LAUNCH_CHECK();
   const int kmax = k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32;  // the self loop is skipped, not
                                                                    // kept, when !loop

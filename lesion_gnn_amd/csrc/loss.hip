@@ -7,24 +7,11 @@
 // One workgroup; rows are summed in fixed order (per-thread strided partials, then a fixed
 // tree), so the loss is bitwise reproducible.
 #include "common.h"
+#include "wg.h"
 
 namespace {
 
 constexpr int CT = 1024;
-
-__device__ __forceinline__ float block_sum_fixed(float v, float* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float t = 0.f;
-  if (threadIdx.x == 0) {
-    for (int w = 0; w < CT / 64; ++w) t += red[w];
-    red[CT / 64] = t;
-  }
-  __syncthreads();
-  return red[CT / 64];
-}
 
 // lse[i] = logsumexp(z_i) (saved for the backward); loss[0] = weighted mean NLL; wsum[0];
 // FACTORS: also the logits gradient's per-row factors pm [B][C], wt [B] (lgnn_ce_src)
@@ -35,7 +22,7 @@ __global__ __launch_bounds__(CT) void k_ce_fwd(const float* __restrict__ z,
                                                float* __restrict__ lse, float* __restrict__ loss,
                                                float* __restrict__ wsum, int* __restrict__ bad,
                                                float* __restrict__ pm, float* __restrict__ wtf) {
-  __shared__ float red[CT / 64 + 1];
+  __shared__ float red[CT / 64];
   if (threadIdx.x == 0) *bad = 0;
   __syncthreads();
   float num = 0.f, den = 0.f;
@@ -60,9 +47,8 @@ __global__ __launch_bounds__(CT) void k_ce_fwd(const float* __restrict__ z,
     num += wt * (l - zi[t]);
     den += wt;
   }
-  const float n = block_sum_fixed(num, red);
-  __syncthreads();
-  const float d = block_sum_fixed(den, red);
+  const float n = block_sum<CT>(num, red);
+  const float d = block_sum<CT>(den, red);
   if (threadIdx.x == 0) {
     loss[0] = n / d;
     wsum[0] = d;
@@ -104,14 +90,14 @@ __global__ __launch_bounds__(CT) void k_reg_fwd(const float* __restrict__ z,
                                                 const T* __restrict__ y, int64_t B, float lo,
                                                 float hi, int smooth, float* __restrict__ pred,
                                                 float* __restrict__ loss) {
-  __shared__ float red[CT / 64 + 1];
+  __shared__ float red[CT / 64];
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < B; i += CT) {
     const float p = fminf(fmaxf(z[i], lo), hi);
     pred[i] = p;
     acc += reg_term(p - target_at(y, i), smooth);
   }
-  const float t = block_sum_fixed(acc, red);
+  const float t = block_sum<CT>(acc, red);
   if (threadIdx.x == 0) loss[0] = t / (float)B;
 }
 

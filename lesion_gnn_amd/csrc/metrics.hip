@@ -13,6 +13,7 @@
 //   k_eval_final   one workgroup: sums the per-sample counts in a fixed order, then thread 0 forms
 //                  every metric in double.
 #include "common.h"
+#include "wg.h"
 
 namespace {
 
@@ -20,29 +21,6 @@ constexpr int CT = 1024;  // k_eval_update / k_eval_final / k_eval_merge: one wo
 constexpr int RB = 256;   // k_eval_rank: samples i per workgroup
 constexpr int T = LGNN_EVAL_RANK_CHUNK;
 constexpr int MAXC = LGNN_EVAL_MAX_CLASSES;
-
-// the sum of v over the workgroup in a fixed order (lanes by xor tree, then waves in order)
-__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();  // red may still be read from a previous call
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < CT / 64; ++w) t += red[w];
-  return t;
-}
-
-__device__ __forceinline__ long long block_sum_i64(long long v, long long* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  long long t = 0;
-  for (int w = 0; w < CT / 64; ++w) t += red[w];
-  return t;
-}
 
 __device__ __forceinline__ float reg_term(float d, int smooth) {  // loss.hip's
   if (!smooth) return d * d;
@@ -132,8 +110,8 @@ __global__ __launch_bounds__(CT) void k_eval_update(const float* __restrict__ z,
     appended += total;
     __syncthreads();  // wcount is rewritten by the next chunk
   }
-  const double nsum = block_sum_fixed(num, red);
-  const double dsum = block_sum_fixed(den, red);
+  const double nsum = block_sum<CT>(num, red);
+  const double dsum = block_sum<CT>(den, red);
   for (int k = tid; k < CC + 4; k += CT)
     if (hist[k]) counts[k] += hist[k];
   if (tid == 0) {
@@ -232,8 +210,8 @@ __global__ __launch_bounds__(CT) void k_eval_final(const int64_t* __restrict__ c
       ap += at_or_above > 0 ? (double)v.z / (double)at_or_above : 0.0;
     }
   }
-  const long long twice_sum = block_sum_i64(twice, ired);
-  const double ap_sum = block_sum_fixed(ap, red);
+  const long long twice_sum = block_sum<CT>(twice, ired);
+  const double ap_sum = block_sum<CT>(ap, red);
   if (tid < C) {
     long long r = 0;
     for (int j = 0; j < C; ++j) r += cnt[tid * C + j];

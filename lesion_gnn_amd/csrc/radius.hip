@@ -25,12 +25,12 @@
 // of its graphs are one contiguous node range, staged through LDS in chunks (as k_knn).
 #include "common.h"
 #include "geom.h"
+#include "wg.h"
 
 namespace {
 
 constexpr int QT = 256;      // queries (threads) per block
 constexpr int CHUNK = 1024;  // candidates staged per round
-constexpr int ST = 1024;     // scan threads
 
 // WRITE = false: cnt[q] = the query's edge count; WRITE = true: its edges at off[q]
 template <int D, bool WRITE>
@@ -86,34 +86,6 @@ __global__ __launch_bounds__(QT) void k_radius(const double* __restrict__ pos, i
   }
 }
 
-// off[i] = sum_{j < i} cnt[j], off[N] = total: one block, each thread a contiguous range
-__global__ __launch_bounds__(ST) void k_radius_scan(const int32_t* __restrict__ cnt, int64_t N,
-                                                    int64_t* __restrict__ off) {
-  __shared__ int64_t part[ST];
-  const int t = threadIdx.x;
-  const int64_t per = (N + ST - 1) / ST;
-  const int64_t i0 = t * per < N ? t * per : N, i1 = i0 + per < N ? i0 + per : N;
-  int64_t s = 0;
-  for (int64_t i = i0; i < i1; ++i) s += cnt[i];
-  part[t] = s;
-  __syncthreads();
-  if (t == 0) {
-    int64_t run = 0;
-    for (int i = 0; i < ST; ++i) {
-      const int64_t v = part[i];
-      part[i] = run;
-      run += v;
-    }
-    off[N] = run;
-  }
-  __syncthreads();
-  int64_t run = part[t];
-  for (int64_t i = i0; i < i1; ++i) {
-    off[i] = run;
-    run += cnt[i];
-  }
-}
-
 struct RadiusWs {
   int64_t* off;  // [N + 1]
   int32_t* cnt;  // [N]
@@ -165,7 +137,7 @@ extern "C" int lgnn_radius_count(const double* pos, int64_t N, int dims, const i
     hipLaunchKernelGGL((k_radius<3, false>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
                        loop, w.cnt, nullptr, 0, nullptr);
   LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(ST), 0, s, w.cnt, N, w.off);
+  launch_exclusive_scan(w.cnt, N, w.off, s);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }
@@ -334,7 +306,7 @@ extern "C" int lgnn_radius_pairs_count(const double* x, int64_t Nx, const double
     hipLaunchKernelGGL((k_radius_pairs<3, false>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
                        (int)B, r2, max_num_neighbors, w.cnt, nullptr, 0, nullptr);
   LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(ST), 0, s, w.cnt, Ny, w.off);
+  launch_exclusive_scan(w.cnt, Ny, w.off, s);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }
@@ -388,7 +360,7 @@ extern "C" int lgnn_pairs_transpose(const int64_t* col, const int64_t* rowoff, i
   hipLaunchKernelGGL(k_pairs_transpose<false>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,
                      (int)B, Nx, cnt, nullptr, nullptr);
   LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_radius_scan, dim3(1), dim3(ST), 0, s, cnt, Nx, tptr);
+  launch_exclusive_scan(cnt, Nx, tptr, s);
   LGNN_LAUNCH_CHECK();
   if (num_pairs > 0) {
     hipLaunchKernelGGL(k_pairs_transpose<true>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,

@@ -31,33 +31,22 @@
 namespace lgnn_s3g {
 using namespace lgnn_tile;
 using lgnn_s3::bf16x2;
+using lgnn_s3::BK;
 using lgnn_s3::f32x2;
+using lgnn_s3::ldb32;
 using lgnn_s3::lds16;
 using lgnn_s3::mfma16;
 using lgnn_s3::mfma_s3;
+using lgnn_s3::OOB;
+using lgnn_s3::opaque;
+using lgnn_s3::ROWB;
 using lgnn_s3::split2;
 using lgnn_s3::Split2;
+using lgnn_s3::swz;
 using lgnn_s3::u32x2;
 
-constexpr int BK = 64;          // k per chunk
-constexpr int ROWB = BK * 2;    // bytes per image row (bf16)
 constexpr int IMG = TM * ROWB;  // bytes per 64-row image plane
-constexpr int OOB = 0x7ff00000;  // buffer offset past every range: loads return 0
 
-// 128-B image rows, 16-B chunk XOR-swizzled by (row >> 1) & 7: the 16 rows of a ds_read_b128
-// lane group ({0-3, 12-15, 20-27} / {4-11, 16-19, 28-31}, MI355X_MICROARCH.md §LDS) land in 16
-// distinct 16-B bank slots (an (row & 7) key pairs rows 8 apart on one slot: 2-way conflicts,
-// measured 40 % extra LDS cycles)
-__device__ __forceinline__ int swz(int row, int chunk) {
-  return row * ROWB + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-__device__ __forceinline__ int opaque(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-__device__ __forceinline__ uint32_t ldb32(Buf b, int off) {
-  return __builtin_amdgcn_raw_buffer_load_b32(b, off, 0, 0);
-}
 __device__ __forceinline__ uint32_t rne16(float v) {  // bf16 bits of v (RNE), low half
   return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2{v, 0.f}), bf16x2)) & 0xffffu;
 }

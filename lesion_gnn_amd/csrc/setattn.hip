@@ -18,6 +18,7 @@
 // The products run on the fp32 VALU (fmaf chains): on gfx950 the fp32 MFMA has the VALU's rate,
 // and bf16 operands would not hold the 1e-4 bar without a split.
 #include "common.h"
+#include "wg.h"
 
 namespace lgnn_setattn {
 
@@ -329,36 +330,25 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// mask_off[g] = heads * sum_{g' < g} nq_g' * nk_g' (one workgroup; each thread scans a contiguous
-// run of sets, the run totals are scanned in LDS)
+// mask_off[g] = heads * sum_{g' < g} nq_g' * nk_g' (one workgroup, tiles of kThreads sets)
 __global__ void __launch_bounds__(kThreads)
     k_mask_offsets(const int32_t* __restrict__ qptr, int q_rows, const int32_t* __restrict__ kptr,
                    int k_rows, int64_t B, int H, int64_t* __restrict__ moff) {
-  __shared__ int64_t tot[kThreads];
-  const int tid = threadIdx.x;
-  const int64_t per = (B + kThreads - 1) / kThreads;
-  const int64_t t0 = tid * per, g0 = t0 < B ? t0 : B, g1 = g0 + per < B ? g0 + per : B;
-  int64_t s = 0;
-  for (int64_t g = g0; g < g1; ++g) {
-    int64_t o;
-    int nq, nk;
-    segment(qptr, q_rows, g, o, nq);
-    segment(kptr, k_rows, g, o, nk);
-    s += (int64_t)H * nq * nk;
+  __shared__ int64_t s_wave[kThreads / 64];
+  int64_t carry = 0;
+  for (int64_t tile = 0; tile < B; tile += kThreads) {
+    const int64_t g = tile + threadIdx.x;
+    int64_t o, n = 0;
+    if (g < B) {
+      int nq, nk;
+      segment(qptr, q_rows, g, o, nq);
+      segment(kptr, k_rows, g, o, nk);
+      n = (int64_t)H * nq * nk;
+    }
+    const int64_t at = block_exclusive_scan<kThreads>(n, carry, s_wave);
+    if (g < B) moff[g] = at;
   }
-  tot[tid] = s;
-  __syncthreads();
-  int64_t base = 0;
-  for (int t = 0; t < tid; ++t) base += tot[t];
-  for (int64_t g = g0; g < g1; ++g) {
-    int64_t o;
-    int nq, nk;
-    segment(qptr, q_rows, g, o, nq);
-    segment(kptr, k_rows, g, o, nk);
-    moff[g] = base;
-    base += (int64_t)H * nq * nk;
-  }
-  if (tid == kThreads - 1) moff[B] = base;
+  if (threadIdx.x == 0) moff[B] = carry;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -369,11 +359,6 @@ constexpr int kMaxC = 512;
 constexpr int kPerLane = kMaxC / 64;
 constexpr int kRowsPerBlock = kThreads / 64;
 constexpr int kMaxParts = 256;
-
-__device__ __forceinline__ float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __device__ __forceinline__ float act_f(float x, int act) {
   return act == LGNN_ACT_RELU ? fmaxf(x, 0.f) : x;

@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "wg.h"
 
 #pragma clang fp contract(off)
 
@@ -278,32 +279,6 @@ __global__ __launch_bounds__(256) void k_extrema(const float* __restrict__ dog, 
     }
   }
   if (!WRITE && lane == 0) counts[row] = total;
-}
-
-// out[0..n] = exclusive scan of in[0..n): one workgroup, 1024 per pass, the carry in order
-__global__ __launch_bounds__(1024) void k_scan(const int32_t* __restrict__ in, int n,
-                                               int32_t* __restrict__ out) {
-  __shared__ int s[1024];
-  __shared__ int carry;
-  const int t = threadIdx.x;
-  if (t == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int v = base + t < n ? in[base + t] : 0;
-    s[t] = v;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-      const int a = t >= d ? s[t - d] : 0;
-      __syncthreads();
-      s[t] += a;
-      __syncthreads();
-    }
-    if (base + t < n) out[base + t] = carry + s[t] - v;
-    __syncthreads();
-    if (t == 1023) carry += s[1023];
-    __syncthreads();
-  }
-  if (t == 0) out[n] = carry;
 }
 
 // ---- refinement -------------------------------------------------------------------------------
@@ -634,17 +609,6 @@ __global__ __launch_bounds__(64) void k_keep(const Keypoint* __restrict__ kp,
   if (alive[j] && kp[j].response >= thr[kp[j].b]) atomicAdd(kept + kp[j].b, 1);
 }
 
-__global__ __launch_bounds__(1024) void k_node_ptr(const int32_t* __restrict__ kept, int batch,
-                                                   int64_t* __restrict__ node_ptr) {
-  if (threadIdx.x != 0) return;
-  int64_t acc = 0;
-  for (int b = 0; b < batch; ++b) {
-    node_ptr[b] = acc;
-    acc += kept[b];
-  }
-  node_ptr[batch] = acc;
-}
-
 // row node_ptr[b] + rank: pt and size halved for the doubled image (exact)
 __global__ __launch_bounds__(64) void k_gather(const Keypoint* __restrict__ kp,
                                                const int32_t* __restrict__ kstart, int batch,
@@ -902,7 +866,7 @@ extern "C" int lgnn_sift_count(const float* dog, int batch, int height, int widt
     k_extrema<false><<<(rows + 3) / 4, 256, 0, st>>>(dog, oc, rows, counts, nullptr, nullptr, 0);
     LGNN_LAUNCH_CHECK();
   }
-  k_scan<<<1, 1024, 0, st>>>(counts, rows, row_ptr);
+  launch_exclusive_scan(counts, rows, row_ptr, st);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }
@@ -947,7 +911,7 @@ extern "C" int lgnn_sift_keypoints(const float* gauss, const float* dog, int bat
     k_orient<<<n, 64, 0, st>>>(gauss, oc, batch, cand, ws.ref, n, ws.npk, ws.angles);
     LGNN_LAUNCH_CHECK();
   }
-  k_scan<<<1, 1024, 0, st>>>(ws.npk, n, ws.koff);
+  launch_exclusive_scan(ws.npk, n, ws.koff, st);
   LGNN_LAUNCH_CHECK();
   k_ranges<<<(batch + 256) / 256, 256, 0, st>>>(cand, n, ws.koff, batch, ws.kstart, ws.thr,
                                                 ws.kept);
@@ -965,7 +929,7 @@ extern "C" int lgnn_sift_keypoints(const float* gauss, const float* dog, int bat
     k_keep<<<blocks, 64, 0, st>>>(ws.kp, ws.kstart, batch, cap, ws.alive, ws.thr, ws.kept);
     LGNN_LAUNCH_CHECK();
   }
-  k_node_ptr<<<1, 64, 0, st>>>(ws.kept, batch, node_ptr);
+  launch_exclusive_scan(ws.kept, batch, node_ptr, st);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }

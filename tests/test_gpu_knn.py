@@ -74,6 +74,16 @@ def test_knn_batches_vs_restatement(cuda, dist, k):
     assert torch.equal(got, b.edge_index)  # make_batch's own k-NN (synth.knn_edges)
 
 
+@pytest.mark.parametrize("B", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_knn_offsets_scan_lengths(cuda, B):
+    """k_knn_offsets at the wave edge, the tile edge (1024 graphs) and with a carry over two
+    tiles: graphs of 1 to 3 nodes, so k is clamped in every one and a single node has no edge."""
+    gen = torch.Generator().manual_seed(B)
+    sizes = torch.randint(1, 4, (B,), generator=gen).tolist()
+    pos = torch.rand(sum(sizes), 2, generator=gen, dtype=torch.float64)
+    assert torch.equal(run(pos, sizes, 2, False, cuda), oracle_batch(pos, sizes, 2, False))
+
+
 def test_knn_large_graph_chunks(cuda):
     gen = torch.Generator().manual_seed(2)
     sizes = [3000, 5, 2500]

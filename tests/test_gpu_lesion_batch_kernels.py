@@ -85,6 +85,30 @@ def test_ccl_batch(cuda, connectivity):
     assert all(torch.equal(a, b) for a, b in zip((labels, num, ptr), again))
 
 
+@functools.lru_cache(maxsize=None)
+def _tiny_images():
+    """2049 seeded 8 x 8 images (one root-count block each), a third of the pixels foreground,
+    every 7th image empty, and their component counts by the restatement (8-connectivity)."""
+    rng = np.random.default_rng(11)
+    imgs = (rng.random((2049, 8, 8)) < 0.33).astype(np.uint8) * rng.integers(1, 4, (2049, 8, 8),
+                                                                               dtype=np.uint8)
+    imgs[::7] = 0
+    return imgs, [ccl_ref.connected_components_with_stats(im, 8)[:2] for im in imgs]
+
+
+@pytest.mark.parametrize("B", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_ccl_batch_scan_lengths(cuda, B):
+    """k_ccl_scan over B block counts, at the wave edge, the tile edge (1024) and with a carry
+    over two tiles: num_labels, node_ptr and the labels of the first B tiny images."""
+    imgs, want = _tiny_images()
+    labels, num, ptr = ops.ccl_batch(torch.from_numpy(imgs[:B]).to(cuda), 8)
+    nl = [w[0] for w in want[:B]]
+    assert len(set(nl)) > 1 or B == 1
+    assert num.tolist() == nl
+    assert ptr.tolist() == [0] + np.cumsum(nl).tolist()
+    assert torch.equal(labels.cpu(), torch.from_numpy(np.stack([w[1] for w in want[:B]])))
+
+
 @pytest.mark.parametrize("connectivity", [4, 8])
 def test_ccl_stats_batch(cuda, connectivity):
     imgs = torch.from_numpy(_ccl_images()).to(cuda)

@@ -155,6 +155,41 @@ def test_out_of_range_id(cuda):
     assert calls == []
 
 
+@pytest.mark.parametrize("num_sel", [0, 1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_scan_lengths(cuda, num_sel):
+    """k_collate_scan at the wave edge, the tile edge (1024 ids) and with a carry over two tiles:
+    ids drawn with repetition from the 37 graphs and three empty ones, every 61st one (and the ids
+    on both sides of the first tile edge) outside the dataset, so the count in err crosses a tile
+    as the offsets do."""
+    x, pos, y, ptr = _host(37, 3, 2)
+    ptr = torch.cat([ptr, ptr[-1:].expand(3)])  # graphs 37, 38, 39: no rows
+    y = torch.cat([y, torch.tensor([0, 1, 2])])
+    host, G = (x, pos, y, ptr), 40
+    store = GraphStore.from_tensors(x.to(cuda), pos.to(cuda), y, ptr)
+    ids = torch.randint(0, G, (num_sel,), generator=torch.Generator().manual_seed(num_sel))
+    bad = [k for k in range(num_sel) if k % 61 == 60 or k in (1023, 1024)]
+    for j, k in enumerate(bad):
+        ids[k] = (G, -1, 1 << 40)[j % 3]
+    where = torch.tensor([k for k in range(num_sel) if k not in bad], dtype=torch.int64)
+    assert num_sel < 100 or bool((ids[where] >= 37).any())  # an empty graph is selected
+    wx, wpos, wy, wbatch, wptr = lr.collate_ref(*host, ids[where].tolist())
+    total = int(wptr[-1])
+    buf = _Buffers(store, num_sel, total + 8)
+    buf.ids[:] = ids
+    buf.call(num_sel, total)
+    assert int(buf.err.item()) == len(bad) < _lib.LGNN_COLLATE_OVERFLOW
+    # a bad id is an empty graph: the good ones keep their batch positions
+    sizes = torch.zeros(num_sel, dtype=torch.int64)
+    sizes[where] = wptr[1:] - wptr[:-1]
+    assert torch.equal(buf.ptr.cpu(), torch.cat([torch.zeros(1, dtype=torch.int64),
+                                                 sizes.cumsum(0)]))
+    assert torch.equal(buf.x[:total].cpu(), wx) and torch.equal(buf.pos[:total].cpu(), wpos)
+    assert torch.equal(buf.batch[:total].cpu(), where[wbatch])
+    assert torch.equal(buf.y.cpu()[where], wy)
+    assert bool((buf.x[total:] == SENTINEL).all())
+    assert bool((buf.batch[total:] == int(SENTINEL)).all())
+
+
 # 4 ---------------------------------------------------------------------------------------------
 
 def test_offsets_past_4gib(cuda):

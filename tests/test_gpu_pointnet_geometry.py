@@ -141,6 +141,17 @@ def test_radius_matches_restatement(cuda, r, max_nn):
     assert torch.equal(got.cpu(), want) and torch.equal(again, got)
 
 
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_radius_scan_lengths(cuda, N):
+    """The counts' scans of lgnn_radius_pairs_count (over the queries) and lgnn_pairs_transpose
+    (over the candidates) at the wave edge, the tile edge (1024) and with a carry over two tiles:
+    every point is a query, so both scans have N elements; graphs of 60 points and an empty one."""
+    sizes = [min(60, N - a) for a in range(0, N, 60)]
+    sizes.insert(1, 0)
+    pos = cases.points(sizes, 2, N)
+    _check_pairs(cuda, pos, pos, sizes, sizes, 0.15, 8)
+
+
 def test_radius_graphs_without_queries_and_queries_without_neighbours(cuda):
     pos, sizes, counts, idx = _radius_points()
     # no query in graphs 0 and 3 (their candidates stay); a far query in graph 5

@@ -83,6 +83,26 @@ def test_radius_graph_edge_cases(cuda):
     assert radius_graph(big[:0].to(cuda), 0.03).numel() == 0
 
 
+@pytest.mark.parametrize("N", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_radius_count_scan_lengths(cuda, N):
+    """The scan of lgnn_radius_count's per-query counts at the wave edge, the tile edge (1024
+    queries) and with a carry over two tiles: graphs of 50 nodes, 0 to 5 neighbours a query."""
+    from lesion_gnn_amd import _lib
+
+    g = torch.Generator().manual_seed(N)
+    sizes = [min(50, N - a) for a in range(0, N, 50)]
+    pos = torch.rand(N, 2, generator=g, dtype=torch.float64) * 100
+    want = check(pos, sizes, 15.0, False, 4, cuda)
+    # the offsets themselves (workspace: off [N + 1] int64, then the counts): the counts' cumsum
+    ws = torch.empty(_lib.load().lgnn_radius_workspace_bytes(N), dtype=torch.uint8, device=cuda)
+    ptr = torch.tensor(ptr_of(sizes), dtype=torch.int32, device=cuda)
+    _lib.call("lgnn_radius_count", pos.to(cuda), N, 2, batch_of(sizes).to(cuda), ptr, len(sizes),
+              15.0, 4, 0, ws, ws.numel(), _lib.stream(cuda))
+    counts = torch.bincount(want[1], minlength=N)
+    assert torch.equal(ws[:8 * (N + 1)].view(torch.int64).cpu(),
+                       torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]))
+
+
 def test_radius_transform_by_name(cuda):
     """transforms.get_transform(TransformConfig(name="RadiusGraph", kwargs={"r": ...})) — how the
     sweep builds it (sweep.py:113-118) — on a collated batch."""

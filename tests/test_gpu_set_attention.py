@@ -168,6 +168,24 @@ def test_dropout_mask_layout_element_by_element(cuda):
     assert moff == [0] + torch.tensor([H * n * n for n in sizes]).cumsum(0).tolist()
 
 
+@pytest.mark.parametrize("B", [0, 1, 63, 64, 65, 255, 256, 257, 513])
+def test_mask_offsets_scan_lengths(cuda, B):
+    """k_mask_offsets (one workgroup of 256 threads) at the wave edge, the tile edge and with a
+    carry over two tiles: ragged query and key sets, some empty; and keys of a fixed size."""
+    from lesion_gnn_amd import ops
+
+    H = 3
+    gen = torch.Generator().manual_seed(B)
+    nq = torch.randint(0, 6, (B,), generator=gen)
+    nk = torch.randint(0, 9, (B,), generator=gen)
+    zero = torch.zeros(1, dtype=torch.int64)
+    qptr, kptr = _ptr(nq.tolist(), cuda), _ptr(nk.tolist(), cuda)
+    moff = ops.set_attn_mask_offsets(ops.AttnForm(qptr, 0, False, kptr, 0, B), H, cuda)
+    assert torch.equal(moff.cpu(), torch.cat([zero, H * (nq * nk).cumsum(0)]))
+    moff = ops.set_attn_mask_offsets(ops.AttnForm(qptr, 0, False, None, 7, B), H, cuda)
+    assert torch.equal(moff.cpu(), torch.cat([zero, H * (nq * 7).cumsum(0)]))
+
+
 @pytest.mark.parametrize("H,D", [(1, 129), (5, 128), (3, 171)])
 def test_out_of_range_shapes_raise(cuda, H, D):
     from lesion_gnn_amd import ops

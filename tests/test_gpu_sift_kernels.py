@@ -124,6 +124,62 @@ def test_keypoints(cuda, name, num_keypoints):
         assert same.all(), (field, np.nonzero(~same)[0][:5], got_kf[~same][:3], want_kf[~same][:3])
 
 
+def _check_noise_batch(cuda, batch, H, W, num_keypoints, sigma=0.8):
+    """A seeded-noise batch through count, candidates and keypoints: row_ptr, the candidate list,
+    the keypoints and node_ptr against the oracle run image by image on the device's pyramid.
+    Returns (scan rows, candidates)."""
+    from lesion_gnn_amd import _lib
+
+    imgs = np.random.default_rng(17 * batch + H).integers(0, 256, (batch, H, W, 3), dtype=np.uint8)
+    pyr = ops.sift_pyramid(torch.from_numpy(imgs).to(cuda), sigma)
+    dims = sift_ref.octave_dims(H, W)
+    per_image = 3 * sum(h for h, _ in dims)
+    rows = _lib.load().lgnn_sift_rows(batch, H, W)
+    assert rows == batch * per_image
+    counts = torch.empty(rows, dtype=torch.int32, device=cuda)
+    row_ptr = torch.empty(rows + 1, dtype=torch.int32, device=cuda)
+    _lib.call("lgnn_sift_count", pyr.dog_flat, batch, H, W, counts, row_ptr, _lib.stream(cuda))
+    gauss = [t.cpu().numpy() for t in pyr.gauss]
+    dog = [t.cpu().numpy() for t in pyr.dog]
+    want_cand = [sift_ref.candidates([d[b] for d in dog]) for b in range(batch)]
+    # a candidate's scan row: image, octave, layer 1..3, row
+    base = np.concatenate([[0], np.cumsum([3 * h for h, _ in dims])])
+    heights = np.array([h for h, _ in dims])
+    per_row = np.zeros(rows, dtype=np.int64)
+    for b, c in enumerate(want_cand):
+        np.add.at(per_row, b * per_image + base[c[:, 0]] + (c[:, 1] - 1) * heights[c[:, 0]] + c[:, 2],
+                  1)
+    assert np.array_equal(row_ptr.cpu().numpy(), np.concatenate([[0], np.cumsum(per_row)]))
+    cand = ops.sift_candidates(pyr)
+    got = cand.cpu().numpy()
+    assert np.array_equal(got[:, 0], np.repeat(np.arange(batch), [len(c) for c in want_cand]))
+    assert np.array_equal(got[:, 1:], np.concatenate(want_cand))
+    kf, ki, ptr, ptr_host = ops.sift_keypoints(pyr, cand, sigma, num_keypoints)
+    want = [sift_ref.keypoints([g[b] for g in gauss], [d[b] for d in dog], sigma, num_keypoints,
+                               cand=want_cand[b]) for b in range(batch)]
+    sizes = [len(w[0]) for w in want]
+    assert ptr_host.tolist() == [0] + np.cumsum(sizes).tolist() and torch.equal(ptr.cpu(), ptr_host)
+    got_ki = ki.cpu().numpy()
+    assert np.array_equal(got_ki[:, 0], np.repeat(np.arange(batch), sizes))
+    assert np.array_equal(got_ki[:, 1:], np.concatenate([w[1] for w in want]))
+    assert np.array_equal(kf.cpu().numpy().view(np.uint32),
+                          np.concatenate([w[0] for w in want]).view(np.uint32))
+    return rows, len(got)
+
+
+def test_scans_past_one_tile(cuda):
+    """More than 1024 scan rows (row_ptr) and more than 1024 candidates (the peak offsets behind
+    the keypoints): both one-workgroup scans carry across a tile."""
+    rows, ncand = _check_noise_batch(cuda, 3, 48, 64, 10000)
+    print(f"{rows} scan rows, {ncand} candidates")
+    assert rows > 1024 and ncand > 1024
+
+
+def test_node_ptr_of_65_images(cuda):
+    """node_ptr past one wave of images, with the response cut at 8 keypoints an image."""
+    _check_noise_batch(cuda, 65, 16, 16, 8)
+
+
 @pytest.mark.parametrize("name", cases.CASE_NAMES)
 def test_descriptors(cuda, name):
     _, _, sigma = cases.case(name)
