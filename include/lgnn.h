@@ -1348,6 +1348,40 @@ int lgnn_collate(const int64_t* ids, int64_t num_sel, const int64_t* src_ptr,
                  int64_t* out_batch, int64_t* out_ptr, int64_t out_capacity, int32_t* err,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* lgnn_collate_edges: the edges of the same selection, for a dataset that keeps each graph's
+ * edges (what PyG's Collater does to edge_index after the per-graph transforms, reference
+ * datamodule.py:43-45,63-69). An addition: the ABI version stays.
+ *   The dataset: edge_index [2, num_src_edges] int64 (row 0 the sources, row 1 the targets, ids
+ *   the dataset's rows), src_edge_ptr [num_src_graphs + 1] int64 (graph g owns the edges
+ *   [src_edge_ptr[g], src_edge_ptr[g + 1]), both endpoints in its rows), src_ptr as above;
+ *   edge_weight [num_src_edges] of weight_bytes (4 or 8) bytes each, or NULL (weight_bytes is not
+ *   read, out_edge_weight is not written). ids, num_sel as above; out_ptr [num_sel + 1]: the
+ *   batch's row offsets as lgnn_collate wrote them for the same ids (same stream, or ordered
+ *   after it).
+ *   With g = ids[b] and m_b = src_edge_ptr[g + 1] - src_edge_ptr[g]: out_edge_ptr [num_sel + 1] =
+ *   the exclusive scan of m_b; for t < m_b and j = out_edge_ptr[b] + t, out_edge_index[:, j] =
+ *   edge_index[:, src_edge_ptr[g] + t] - src_ptr[g] + out_ptr[b] and out_edge_weight[j] = the
+ *   source element, copied bit for bit.
+ *   out_capacity: the edges out_edge_index [2, out_capacity] and out_edge_weight hold (the row
+ *   stride of out_edge_index). The edge total is read on the device (a captured call replays on
+ *   refilled ids): edges at or beyond it are left untouched, and nothing is written at or beyond
+ *   edge out_capacity. A source position outside [0, num_src_edges) is skipped.
+ *   err [1] int32, written: the number of ids outside [0, num_src_graphs) (each counts as a graph
+ *   without edges), plus LGNN_COLLATE_OVERFLOW when the total exceeds out_capacity (out_edge_ptr
+ *   is complete all the same).
+ *   workspace: lgnn_collate_edges_workspace_bytes(num_sel), never 0. num_sel = 0 writes
+ *   out_edge_ptr[0] = 0 and err. Three launches (the gather is skipped when num_sel,
+ *   out_capacity or num_src_edges is 0), no host synchronisation. LGNN_EINVAL, before any
+ *   launch: a negative count, a NULL required pointer, weights with weight_bytes not 4 or 8 or
+ *   without out_edge_weight, a workspace that is too small. */
+size_t lgnn_collate_edges_workspace_bytes(int64_t num_sel);
+int lgnn_collate_edges(const int64_t* ids, int64_t num_sel, const int64_t* src_ptr,
+                       const int64_t* src_edge_ptr, int64_t num_src_graphs,
+                       const int64_t* edge_index, int64_t num_src_edges, const void* edge_weight,
+                       int weight_bytes, const int64_t* out_ptr, int64_t* out_edge_index,
+                       void* out_edge_weight, int64_t* out_edge_ptr, int64_t out_capacity,
+                       int32_t* err, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * SIFT nodes for a batch of images of one size. Replaces: cv2.SIFT_create(nfeatures,
  * contrastThreshold = 0, sigma).detectAndCompute of the reference's SiftExtractor

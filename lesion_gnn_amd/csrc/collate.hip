@@ -232,6 +232,86 @@ __global__ __launch_bounds__(kT) void k_collate_gather(
   }
 }
 
+// ---- edges (lgnn_collate_edges) ---------------------------------------------------------------
+// A store that keeps each graph's edges (GraphStore.with_edges) has them contiguous per graph, so
+// inside selected graph b the output edge j is the source edge j + edelta[b], and both endpoints
+// move by shift[b] = out_ptr[b] - src_ptr[ids[b]]. Three launches, shaped as the three above:
+// k_collate_edge_sizes (one thread per selected graph), k_collate_scan itself for out_edge_ptr,
+// and k_collate_edge_gather, cut by output edges, not by graph: workgroup c owns the output edges
+// [c * kEdgeChunk, (c + 1) * kEdgeChunk) whatever graphs they fall in (a graph has 0 to a few
+// thousand edges; a workgroup per graph would idle 255 lanes on a one-edge graph and serialise a
+// 3000-edge one). It finds the graphs of its first and last edge with graph_of_row_wg, each thread
+// bisects that short range. Thread t's u-th edge is c * kEdgeChunk + u * kT + t, so every wave
+// store of either row is 64 consecutive int64 (512 B); the loads are as contiguous as the graphs
+// are. An edge's source position is at any 8-byte offset, so 16-byte accesses would need the
+// pairing of k_collate_gather for a payload 100 times smaller than x: not done.
+
+constexpr int kEdgesPer = 4;               // edges per thread, all loads in flight before a store
+constexpr int kEdgeChunk = kT * kEdgesPer;
+
+// Per selected graph b: its edge count into out_edge_ptr[b] (-1 for an id outside the dataset or
+// a negative count), its first source edge into efirst[b], its endpoint shift into shift[b].
+__global__ __launch_bounds__(kT) void k_collate_edge_sizes(
+    const int64_t* __restrict__ ids, int64_t num_sel, const int64_t* __restrict__ src_ptr,
+    const int64_t* __restrict__ src_edge_ptr, int64_t num_src, const int64_t* __restrict__ out_ptr,
+    int64_t* __restrict__ out_edge_ptr, int64_t* __restrict__ efirst,
+    int64_t* __restrict__ shift) {
+  const int64_t b = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (b >= num_sel) return;
+  const int64_t id = ids[b];
+  const bool ok = id >= 0 && id < num_src;
+  const int64_t first = ok ? src_edge_ptr[id] : 0;
+  const int64_t m = ok ? src_edge_ptr[id + 1] - first : -1;
+  out_edge_ptr[b] = m >= 0 ? m : -1;
+  efirst[b] = first;
+  shift[b] = ok ? out_ptr[b] - src_ptr[id] : 0;
+}
+
+template <typename W>
+__global__ __launch_bounds__(kT) void k_collate_edge_gather(
+    const int64_t* __restrict__ edge_index, int64_t num_src_edges, const W* __restrict__ weight,
+    const int64_t* __restrict__ out_edge_ptr, const int64_t* __restrict__ edelta,
+    const int64_t* __restrict__ shift, int64_t num_sel, int64_t* __restrict__ out_edge_index,
+    W* __restrict__ out_weight, int64_t capacity) {
+  const int64_t total = out_edge_ptr[num_sel];
+  const int64_t edges = total < capacity ? total : capacity;  // nothing at or beyond either
+  const int64_t j0 = (int64_t)blockIdx.x * kEdgeChunk;
+  if (j0 >= edges) return;
+  const int64_t j1 = j0 + kEdgeChunk < edges ? j0 + kEdgeChunk : edges;
+  const int64_t g_lo = graph_of_row_wg(out_edge_ptr, num_sel, j0);
+  const int64_t g_hi = graph_of_row_wg(out_edge_ptr, num_sel, j1 - 1);
+  int64_t src[kEdgesPer], sh[kEdgesPer];
+  int64_t gc = g_lo;
+#pragma unroll
+  for (int u = 0; u < kEdgesPer; ++u) {
+    const int64_t j = j0 + u * kT + threadIdx.x;
+    src[u] = -1;
+    sh[u] = 0;
+    if (j >= j1) continue;
+    gc = graph_of_row(out_edge_ptr, gc, g_hi, j);  // a thread's edges ascend
+    const int64_t e = j + edelta[gc];
+    if (e >= 0 && e < num_src_edges) src[u] = e;  // a src_edge_ptr beyond edge_index reads nothing
+    sh[u] = shift[gc];
+  }
+  int64_t s[kEdgesPer], t[kEdgesPer];
+  W w[kEdgesPer];
+#pragma unroll
+  for (int u = 0; u < kEdgesPer; ++u) {
+    if (src[u] < 0) continue;
+    s[u] = edge_index[src[u]];
+    t[u] = edge_index[num_src_edges + src[u]];
+    if (weight) w[u] = weight[src[u]];
+  }
+#pragma unroll
+  for (int u = 0; u < kEdgesPer; ++u) {
+    if (src[u] < 0) continue;
+    const int64_t j = j0 + u * kT + threadIdx.x;
+    out_edge_index[j] = s[u] + sh[u];
+    out_edge_index[capacity + j] = t[u] + sh[u];
+    if (weight) out_weight[j] = w[u];
+  }
+}
+
 }  // namespace
 
 extern "C" size_t lgnn_collate_workspace_bytes(int64_t num_sel) {
@@ -274,6 +354,58 @@ extern "C" int lgnn_collate(const int64_t* ids, int64_t num_sel, const int64_t* 
   hipLaunchKernelGGL(k_collate_gather, dim3((unsigned)(x_blocks + row_blocks)), dim3(kT), 0,
                      as_stream(stream), x, channels, pos, dims, out_ptr, delta, num_sel, out_x,
                      out_pos, out_batch, out_capacity, x_blocks);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
+
+extern "C" size_t lgnn_collate_edges_workspace_bytes(int64_t num_sel) {
+  // efirst / edelta [num_sel] and shift [num_sel]; never 0, so that a caller's buffer has an address
+  return ((size_t)(num_sel > 0 ? num_sel : 0) * 2 + 2) * sizeof(int64_t);
+}
+
+extern "C" int lgnn_collate_edges(const int64_t* ids, int64_t num_sel, const int64_t* src_ptr,
+                                  const int64_t* src_edge_ptr, int64_t num_src_graphs,
+                                  const int64_t* edge_index, int64_t num_src_edges,
+                                  const void* edge_weight, int weight_bytes,
+                                  const int64_t* out_ptr, int64_t* out_edge_index,
+                                  void* out_edge_weight, int64_t* out_edge_ptr,
+                                  int64_t out_capacity, int32_t* err, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  if (num_sel < 0 || num_src_graphs < 0 || num_src_edges < 0 || out_capacity < 0)
+    return LGNN_EINVAL;
+  if (!out_edge_ptr || !err || !src_ptr || !src_edge_ptr || !workspace) return LGNN_EINVAL;
+  if (num_sel > 0 && (!ids || !out_ptr)) return LGNN_EINVAL;
+  if (num_sel > 0 && out_capacity > 0 && num_src_edges > 0 && (!edge_index || !out_edge_index))
+    return LGNN_EINVAL;
+  if (edge_weight && ((weight_bytes != 4 && weight_bytes != 8) || !out_edge_weight))
+    return LGNN_EINVAL;
+  if (workspace_bytes < lgnn_collate_edges_workspace_bytes(num_sel)) return LGNN_EINVAL;
+  const int64_t blocks = (out_capacity + kEdgeChunk - 1) / kEdgeChunk;
+  if (blocks > 0x7fffffff || (num_sel + kT - 1) / kT > 0x7fffffff) return LGNN_EINVAL;
+  int64_t* edelta = static_cast<int64_t*>(workspace);
+  int64_t* shift = edelta + num_sel;
+  if (num_sel > 0) {
+    hipLaunchKernelGGL(k_collate_edge_sizes, dim3((unsigned)((num_sel + kT - 1) / kT)), dim3(kT),
+                       0, as_stream(stream), ids, num_sel, src_ptr, src_edge_ptr, num_src_graphs,
+                       out_ptr, out_edge_ptr, edelta, shift);
+    LGNN_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_collate_scan, dim3(1), dim3(kScanT), 0, as_stream(stream), num_sel,
+                     out_edge_ptr, edelta, out_capacity, err);
+  LGNN_LAUNCH_CHECK();
+  if (num_sel == 0 || out_capacity == 0 || num_src_edges == 0) return LGNN_OK;
+  if (edge_weight && weight_bytes == 8)
+    hipLaunchKernelGGL(k_collate_edge_gather<uint64_t>, dim3((unsigned)blocks), dim3(kT), 0,
+                       as_stream(stream), edge_index, num_src_edges,
+                       static_cast<const uint64_t*>(edge_weight), out_edge_ptr, edelta, shift,
+                       num_sel, out_edge_index, static_cast<uint64_t*>(out_edge_weight),
+                       out_capacity);
+  else
+    hipLaunchKernelGGL(k_collate_edge_gather<uint32_t>, dim3((unsigned)blocks), dim3(kT), 0,
+                       as_stream(stream), edge_index, num_src_edges,
+                       static_cast<const uint32_t*>(edge_weight), out_edge_ptr, edelta, shift,
+                       num_sel, out_edge_index, static_cast<uint32_t*>(out_edge_weight),
+                       out_capacity);
   LGNN_LAUNCH_CHECK();
   return LGNN_OK;
 }

@@ -8,9 +8,10 @@ resident on the GPU, `GraphLoader`, which shuffles it and collates each batch in
 (ops.collate), and `DataModule` (datamodule.py). The node extractor's kernels are under
 nodes.lesions.
 """
-from .datamodule import DataConfig, DataModule, compose_transforms
+from .datamodule import DataConfig, DataModule, compose_transforms, hoisted_transforms
 from .memory import (ConcatGraphs, GraphLoader, GraphStore, batch_bounds, class_weights,
                      epoch_order)
 
 __all__ = ["ConcatGraphs", "DataConfig", "DataModule", "GraphLoader", "GraphStore",
-           "batch_bounds", "class_weights", "compose_transforms", "epoch_order"]
+           "batch_bounds", "class_weights", "compose_transforms", "epoch_order",
+           "hoisted_transforms"]

@@ -184,9 +184,10 @@ class BaseModule(nn.Module):
 
     def validation_step(self, batch, batch_idx: int = 0, dataloader_idx: int = 0,
                         dataset_name: str | None = None) -> None:
-        """Reference base.py:203-216 (the dataset name is an argument here: there is no trainer
-        to ask; it defaults to str(dataloader_idx)). One model forward and one launch, no host
-        synchronisation; the values are read by epoch_metrics("val")."""
+        """Reference base.py:203-216 (the dataset name is an argument here, passed by
+        training.Trainer from its loader dict; it defaults to str(dataloader_idx)). One model
+        forward and one launch, no host synchronisation; the values are read by
+        epoch_metrics("val")."""
         self._evaluate("val", batch, dataloader_idx, dataset_name)
 
     def test_step(self, batch, batch_idx: int = 0, dataloader_idx: int = 0,

@@ -2468,13 +2468,18 @@ def cc_pool_resample(features: torch.Tensor, labels: torch.Tensor, node_ptr: tor
     return (out, counts) if return_counts else out
 
 
-def collate(store, ids, validate: bool = False):
+def collate(store, ids, validate: bool = False, ids_dev: torch.Tensor | None = None):
     """The graphs `ids` (host int64 tensor or list; repeats allowed) of a datasets.GraphStore as
     one synth.Batch on the store's device (lgnn_collate): x, pos, y, batch, ptr as PyG's Collater
-    gives them, an empty [2, 0] edge_index and num_graphs set. An id outside [0, len(store))
-    raises IndexError before any launch. The output is sized from the store's host copy of ptr:
-    nothing is read back from the device, unless validate, which reads err and raises if the
-    kernel skipped an id or ran out of rows."""
+    gives them and num_graphs set. A store with edges (GraphStore.with_edges) gives edge_index
+    [2, sum m_b] too, the graphs' edges offset to the batch's rows (lgnn_collate_edges, on the same
+    stream), `batch.edge_ptr` and, when the store has weights, `batch.edge_weight`; a store without
+    gives an empty [2, 0] edge_index and no further launch. An id outside [0, len(store)) raises
+    IndexError before any launch. The outputs are sized from the store's host copies of ptr and
+    edge_ptr: nothing is read back from the device, unless validate, which reads both err words
+    and raises if a kernel skipped an id or ran out of room. ids_dev: the same ids already on the
+    device (GraphLoader uploads an epoch's order once, without a synchronising copy); by default
+    they are copied there."""
     from .synth import Batch
 
     ids = torch.as_tensor(ids, dtype=torch.int64, device="cpu").reshape(-1)
@@ -2498,19 +2503,53 @@ def collate(store, ids, validate: bool = False):
             pos = torch.zeros(1, dims, dtype=torch.float64, device=dev)
     out_y = torch.empty(max(B, 1), dtype=torch.int64, device=dev)
     out_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
-    err = torch.empty(1, dtype=torch.int32, device=dev)
+    err = torch.empty(2, dtype=torch.int32, device=dev)  # [rows, edges]
     nws = _lib.load().lgnn_collate_workspace_bytes(B)
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
-    ids_dev = ids.to(dev)
+    if ids_dev is None:
+        ids_dev = ids.to(dev)
+    elif ids_dev.dtype != torch.int64 or ids_dev.device != dev or ids_dev.shape != ids.shape \
+            or not ids_dev.is_contiguous():
+        raise ValueError("collate: ids_dev must be the ids as a contiguous int64 tensor on the "
+                         "store's device")
     _lib.call("lgnn_collate", ids_dev if B else None, B, store.ptr, G, x, C, pos, dims,
               store.y if G else out_y, out_x, out_pos, out_y, out_batch, out_ptr, total, err, ws,
               nws, _s(dev))
-    if validate and int(err.item()):
-        raise IndexError(f"collate: err = {int(err.item())} (ids the kernel skipped, plus "
-                         f"{_lib.LGNN_COLLATE_OVERFLOW} if the rows overflowed)")
-    return Batch(out_x[:total], torch.empty(2, 0, dtype=torch.int64, device=dev),
-                 out_batch[:total], out_ptr, out_y[:B],
-                 None if out_pos is None else out_pos[:total], B)
+    edge_index = edge_ptr = edge_weight = None
+    if getattr(store, "edge_index", None) is not None:
+        m = store.edge_ptr_host[ids + 1] - store.edge_ptr_host[ids]
+        E, w = int(m.sum()), store.edge_weight
+        edge_index = torch.empty(2, max(E, 1), dtype=torch.int64, device=dev)
+        edge_ptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+        if w is not None:
+            edge_weight = torch.empty(max(E, 1), dtype=w.dtype, device=dev)
+        ews = torch.empty(_lib.load().lgnn_collate_edges_workspace_bytes(B), dtype=torch.uint8,
+                          device=dev)
+        has_w = w is not None and w.numel() > 0
+        # the row stride of the output is the capacity: E edges exactly, unless E is 0, when
+        # nothing is written
+        _lib.call("lgnn_collate_edges", ids_dev if B else None, B, store.ptr, store.edge_ptr, G,
+                  store.edge_index if store.edge_index.numel() else None,
+                  store.edge_index.size(1), w if has_w else None, w.element_size() if has_w else 0,
+                  out_ptr, edge_index, edge_weight if has_w else None, edge_ptr, E, err[1:], ews,
+                  ews.numel(), _s(dev))
+        edge_index = edge_index[:, :E]
+        edge_weight = None if edge_weight is None else edge_weight[:E]
+    if validate:
+        e = err.tolist()
+        e[1] = e[1] if edge_ptr is not None else 0  # written only for a store with edges
+        if e[0] or e[1]:
+            raise IndexError(f"collate: err = {e[0]} for the rows, {e[1]} for the edges (ids the "
+                             f"kernel skipped, plus {_lib.LGNN_COLLATE_OVERFLOW} on overflow)")
+    if edge_index is None:
+        edge_index = torch.empty(2, 0, dtype=torch.int64, device=dev)
+    out = Batch(out_x[:total], edge_index, out_batch[:total], out_ptr, out_y[:B],
+                None if out_pos is None else out_pos[:total], B)
+    if edge_ptr is not None:
+        out.edge_ptr = edge_ptr
+    if edge_weight is not None:
+        out.edge_weight = edge_weight
+    return out
 
 
 # ----------------------------------------------------------------------------------------------
