@@ -876,6 +876,11 @@ int lgnn_mask_mul(const float* x, const float* mask, float* y, int64_t n, void* 
  * (act = LGNN_ACT_ELU: 1 where H > 0, H + 1 elsewhere — F.elu's autograd, reference gin.py:31);
  * n floats, 16-B aligned; dZ may alias dY */
 int lgnn_act_bwd(const float* dY, const float* H, float* dZ, int64_t n, int act, void* stream);
+/* lgnn_add_act: y = act(a + b) over n floats (act = LGNN_ACT_ELU): the sum of GraphConv's two
+ * branches (lin_rel's aggregation and lin_root, reference drgnet.py:33-36) with the F.elu DRGNet
+ * applies to it (drgnet.py:57), so that the eager and the compiled model run the same kernel
+ * there. Its backward is lgnn_act_bwd from y, handed to both branches. */
+int lgnn_add_act(const float* a, const float* b, float* y, int64_t n, int act, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Sort pooling (DGCNN). Replaces: PyG 2.5.1 SortAggregation(k) as DRGNet applies it to the
@@ -896,6 +901,48 @@ int lgnn_sort_pool_fwd(const float* x, int64_t num_nodes, int dims, const int32_
 int lgnn_sort_pool_bwd(const float* dout, const float* x, const int32_t* rank,
                        const int64_t* batch, const float* fill, int64_t num_nodes, int dims,
                        int k, float* dx, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DRGNet head. Replaces: the torch modules DRGNet runs after SortAggregation (reference
+ * src/lesion_gnn/models/drgnet.py:38-48, called at :60-64): Conv1d(1, c0, D, stride D) -> ELU ->
+ * MaxPool1d(2, 2) -> Conv1d(c0, c1, 5) -> ELU -> flatten -> Lin(dense, H) -> ELU -> dropout ->
+ * Lin(H, C), i.e. MIOpen convolutions, hipBLAS linears and the elementwise launches between them.
+ *   x [B, k*D] fp32, the sort-pooled rows (row r of graph b at x[b, r*D ..)); conv1_w [c0, 1, D],
+ *   conv2_w [c1, c0, 5], lin0_w [H, dense], lin1_w [C, H] and their biases, as the modules hold
+ *   them. K2 = k / 2 (an odd k drops its last row, as MaxPool1d does), P = K2 - 4,
+ *   dense = c1 * P (anything else: LGNN_EINVAL). mask (nullable) [B, H]: the dropout mask, 0 or
+ *   1 / (1 - p), applied after Lin0's ELU. logits [B, C].
+ *   Saved by the forward for the backward: a1 [B, K2, c0] (pooled ELU outputs), sel
+ *   [B, K2, ceil(c0 / 16)] (bit i % 16 of word i / 16: the pool took the SECOND row of the pair
+ *   for channel i; a tie takes the first, as torch's max_pool1d), a2 [B, dense], h [B, H] (Lin0's
+ *   ELU output before the mask).
+ * Limits (else LGNN_EINVAL, before any launch): 1 <= D <= 4097, 10 <= k <= 512, 1 <= c0, c1 <= 64,
+ *   1 <= H <= 256, 1 <= C <= 16, B >= 1; for the backward also (B + 64) * max(dense, H + 1) < 2^29
+ *   (the weight-gradient GEMM's 32-bit offsets). One launch.
+ * lgnn_drgnet_head_bwd: dx [B, k*D] (the dropped row of an odd k: exactly 0) and the eight
+ *   parameter gradients from dlogits [B, C]. He = H + H % 2: dlin0_w has room for [He, dense],
+ *   dlin0_b for [He] floats (the first H rows are the gradient), dh [B, He] is scratch (Lin0's
+ *   pre-activation gradient). No floating-point atomics; every sum in a fixed order (bitwise
+ *   reproducible). Workspace: lgnn_drgnet_head_workspace_bytes (0: unsupported shape), at most
+ *   512 slabs of the small gradients and lgnn_s3_wgrad's slabs of dlin0_w, whatever B. Three
+ *   launches: the per-graph kernel, lgnn_s3_wgrad, lgnn_reduce_partials_multi.
+ * ------------------------------------------------------------------------------------------- */
+size_t lgnn_drgnet_head_workspace_bytes(int64_t num_graphs, int k, int dims, int c0, int c1,
+                                        int hidden, int classes);
+int lgnn_drgnet_head_fwd(const float* x, int64_t num_graphs, int k, int dims,
+                         const float* conv1_w, const float* conv1_b, int c0,
+                         const float* conv2_w, const float* conv2_b, int c1, const float* lin0_w,
+                         const float* lin0_b, int hidden, int dense, const float* lin1_w,
+                         const float* lin1_b, int classes, const float* mask, float* logits,
+                         float* a1, uint16_t* sel, float* a2, float* h, void* stream);
+int lgnn_drgnet_head_bwd(const float* dlogits, const float* x, int64_t num_graphs, int k, int dims,
+                         const float* conv1_w, int c0, const float* conv2_w, int c1,
+                         const float* lin0_w, int hidden, int dense, const float* lin1_w,
+                         int classes, const float* mask, const float* a1, const uint16_t* sel,
+                         const float* a2, const float* h, float* dx, float* dh, float* dconv1_w,
+                         float* dconv1_b, float* dconv2_w, float* dconv2_b, float* dlin0_w,
+                         float* dlin0_b, float* dlin1_w, float* dlin1_b, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Lesion-node feature pooling. Replaces: extract_features_by_cc (reference

@@ -56,14 +56,22 @@ class GraphConv(nn.Module):
         self.lin_rel = nn.Linear(in_channels, out_channels, bias=True)
         self.lin_root = nn.Linear(in_channels, out_channels, bias=False)
 
-    def forward(self, x: torch.Tensor, edge_index, edge_weight: torch.Tensor | None = None
-                ) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, edge_index, edge_weight: torch.Tensor | None = None,
+                elu: bool = False) -> torch.Tensor:
+        """elu=True returns ELU(out) with the sum of the two branches and the activation as one
+        HIP launch (ops.add_elu) and the bias inside a Linear kernel on every route, so that no
+        torch elementwise op stands between the lgnn ops (DRGNet: eager and compiled then run the
+        same kernels)."""
         _lib.require_gpu(x)
         g = as_graph(edge_index, x.size(0))
         if edge_weight is None and g.adj_values is not None:  # weighted adj_t (ToSparseTensor)
             edge_weight = g.adj_values
         kind = g.weighted(edge_weight) if edge_weight is not None else "gin"
         K, N = self.in_channels, self.out_channels
+        if elu and not (K % 4 == 0 and (N % 4 != 0 or K <= N)) and N % 4 == 0:
+            # lin_rel's bias rides on lin_root's kernel (the aggregation comes after lin_rel here)
+            root = ops.linear_auto(x, self.lin_root.weight, self.lin_rel.bias)
+            return ops.add_elu(ops.spmm(ops.linear_auto(x, self.lin_rel.weight), g, kind), root)
         root = ops.linear_auto(x, self.lin_root.weight)
         if K % 4 == 0 and (N % 4 != 0 or K <= N):
             rel = ops.linear_auto(ops.spmm(x, g, kind), self.lin_rel.weight, self.lin_rel.bias)
@@ -73,7 +81,7 @@ class GraphConv(nn.Module):
             pad = (-K) % 4
             agg = ops.spmm(torch.nn.functional.pad(x, (0, pad)), g, kind)[:, :K]
             rel = ops.linear_auto(agg, self.lin_rel.weight, self.lin_rel.bias)
-        return rel + root
+        return ops.add_elu(rel, root) if elu else rel + root
 
 
 class BatchNorm(nn.Module):

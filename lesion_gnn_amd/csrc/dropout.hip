@@ -113,7 +113,27 @@ __global__ __launch_bounds__(kT) void k_act_bwd(const float* __restrict__ dy,
   }
 }
 
+// Y = ELU(A + B): the sum of a conv's two branches and its activation
+__global__ __launch_bounds__(kT) void k_add_act(const float* __restrict__ a,
+                                                const float* __restrict__ b, int64_t n,
+                                                float* __restrict__ y) {
+  const int64_t stride = (int64_t)gridDim.x * kT;
+  for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < n; i += stride)
+    y[i] = elu_f(a[i] + b[i]);
+}
+
 }  // namespace
+
+extern "C" int lgnn_add_act(const float* a, const float* b, float* y, int64_t n, int act,
+                            void* stream) {
+  if (n < 0 || act != LGNN_ACT_ELU || (n > 0 && (!a || !b || !y))) return LGNN_EINVAL;
+  if (n == 0) return LGNN_OK;
+  int64_t nb = (n + kT - 1) / kT;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(k_add_act, dim3((unsigned)nb), dim3(kT), 0, as_stream(stream), a, b, n, y);
+  LGNN_LAUNCH_CHECK();
+  return LGNN_OK;
+}
 
 extern "C" int lgnn_act_bwd(const float* dy, const float* h, float* dz, int64_t n, int act,
                             void* stream) {

@@ -837,6 +837,95 @@ def _sort_backward(ctx, grads):
 sort_pool.register_autograd(_sort_backward, setup_context=_sort_setup)
 
 
+# ----------------------------------------------------------------------------------------------
+# ELU(a + b): GraphConv's two branches and the activation after it
+# ----------------------------------------------------------------------------------------------
+
+
+@custom_op("lgnn::add_elu", mutates_args=(), device_types="cuda")
+def add_elu(a: Tensor, b: Tensor) -> Tensor:
+    return ops.add_act_fwd(a, b)
+
+
+@add_elu.register_fake
+def _(a, b):
+    return torch.empty_like(a, memory_format=torch.contiguous_format)
+
+
+@custom_op("lgnn::add_elu_bwd", mutates_args=(), device_types="cuda")
+def add_elu_bwd(dy: Tensor, y: Tensor) -> Tensor:
+    return ops.add_act_bwd(dy.contiguous(), y)
+
+
+@add_elu_bwd.register_fake
+def _(dy, y):
+    return torch.empty_like(y)
+
+
+def _add_elu_setup(ctx, inputs, output):
+    ctx.save_for_backward(output)
+
+
+def _add_elu_backward(ctx, grad):
+    dz = torch.ops.lgnn.add_elu_bwd(grad, ctx.saved_tensors[0])
+    return dz, dz
+
+
+add_elu.register_autograd(_add_elu_backward, setup_context=_add_elu_setup)
+
+
+# ----------------------------------------------------------------------------------------------
+# DRGNet head
+# ----------------------------------------------------------------------------------------------
+
+
+@custom_op("lgnn::drgnet_head", mutates_args=(), device_types="cuda")
+def drgnet_head(x: Tensor, k: int, params: list[Tensor], mask: Optional[Tensor]) -> list[Tensor]:
+    """[logits, a1, sel, a2, h] (ops.drgnet_head_fwd and what it saves)."""
+    logits, sv = ops.drgnet_head_fwd(x, k, tuple(params), mask)
+    return [logits, sv.a1, sv.sel, sv.a2, sv.h]
+
+
+@drgnet_head.register_fake
+def _(x, k, params, mask):
+    B, D, c0, c1, H, dense, C = ops.drgnet_head_dims(x, k, params, mask)
+    return [x.new_empty(B, C), x.new_empty(B, k // 2, c0),
+            x.new_empty(B, k // 2, (c0 + 15) // 16, dtype=torch.int16), x.new_empty(B, dense),
+            x.new_empty(B, H)]
+
+
+@custom_op("lgnn::drgnet_head_bwd", mutates_args=(), device_types="cuda")
+def drgnet_head_bwd(dlogits: Tensor, x: Tensor, k: int, params: list[Tensor],
+                    mask: Optional[Tensor], a1: Tensor, sel: Tensor, a2: Tensor,
+                    h: Tensor) -> list[Tensor]:
+    """[dx, the eight parameter gradients]"""
+    sv = ops.DrgHeadSaved(x.contiguous(), k, tuple(p.contiguous() for p in params), mask, a1, sel,
+                          a2, h)
+    dx, dparams = ops.drgnet_head_bwd(sv, dlogits.contiguous())
+    return [dx] + dparams
+
+
+@drgnet_head_bwd.register_fake
+def _(dlogits, x, k, params, mask, a1, sel, a2, h):
+    return [torch.empty_like(x)] + [torch.empty_like(p) for p in params]
+
+
+def _head_setup(ctx, inputs, output):
+    x, k, params, mask = inputs
+    ctx.save_for_backward(x, *output[1:], *params, *([] if mask is None else [mask]))
+    ctx.k, ctx.npar = k, len(params)
+
+
+def _head_backward(ctx, grads):
+    x, a1, sel, a2, h, *rest = ctx.saved_tensors
+    params, mask = rest[:ctx.npar], (rest[ctx.npar] if len(rest) > ctx.npar else None)
+    out = torch.ops.lgnn.drgnet_head_bwd(grads[0], x, ctx.k, list(params), mask, a1, sel, a2, h)
+    return out[0], None, list(out[1:]), None
+
+
+drgnet_head.register_autograd(_head_backward, setup_context=_head_setup)
+
+
 def gparts_empty(dev) -> list[Tensor]:
     return [_none(dev) for _ in GPARTS]
 

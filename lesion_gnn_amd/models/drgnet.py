@@ -6,10 +6,14 @@ Conv1d / MLP head over the k sorted node rows.
 On the GPU: every GraphConv is the HIP weighted segmented sum (lgnn_spmm, transpose CSR in the
 backward) + the node-linear kernels or the library GEMM for the 1025-wide input layer; the graph
 is built once (one `Graph` shared by every conv, the weighted CSR cached per weight tensor);
-SortAggregation is lgnn_sort_pool_fwd/_bwd. The head (B x k rows, a few KFLOP per graph) runs on
-torch's GPU Conv1d / MaxPool1d / Linear, as the reference's own modules do — same state_dict keys:
-graph_convs.{i}.lin_rel.{weight,bias}, graph_convs.{i}.lin_root.weight, conv1.*, conv2.*,
-mlp.lins.{0,1}.*.
+SortAggregation is lgnn_sort_pool_fwd/_bwd. The head (Conv1d / ELU / MaxPool1d / Conv1d / ELU / Lin /
+ELU / dropout / Lin over the B x k sorted rows) is ops.drgnet_head: lgnn_drgnet_head_fwd, one launch,
+and lgnn_drgnet_head_bwd, three (csrc/drgnet_head.hip). conv1, conv2 and mlp.lins only hold the
+parameters, so the state_dict keys are the reference's: graph_convs.{i}.lin_rel.{weight,bias},
+graph_convs.{i}.lin_root.weight, conv1.*, conv2.*, mlp.lins.{0,1}.*. The head's dropout mask
+comes from the package's counter-based generator (lesion_gnn_amd.dropout; the non-persistent buffer
+`_dropout_rng`): one lgnn_dropout_masks launch per training forward, none in eval or with p = 0,
+and the oracle regenerates the mask from (seed, counter).
 """
 from __future__ import annotations
 
@@ -18,9 +22,10 @@ from itertools import pairwise
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from ..conv import GraphConv, SortAggregation
+from .. import dropout as lgnn_dropout
+from .. import ops
+from ..conv import GraphConv, SortAggregation, dropout_state
 from ..graph import as_graph
 from ..utils.placeholder import Placeholder
 from .base import BaseModelConfig, BaseModule
@@ -28,7 +33,9 @@ from .base import BaseModelConfig, BaseModule
 
 class MLP(nn.Module):
     """PyG 2.5.1 MLP(channel_list, dropout, norm=None, act=F.elu) with plain_last=True
-    (reference drgnet.py:48): Lin -> ELU -> Dropout -> ... -> Lin; keys lins.{i}.*."""
+    (reference drgnet.py:48): Lin -> ELU -> Dropout -> Lin; keys lins.{i}.*. A parameter
+    container: the head kernel (ops.drgnet_head) reads lins.0 / lins.1 and applies the dropout
+    mask, so there is no torch route through it."""
 
     def __init__(self, channel_list: list[int], dropout: float = 0.0):
         super().__init__()
@@ -37,9 +44,8 @@ class MLP(nn.Module):
         self.lins = nn.ModuleList([nn.Linear(a, b) for a, b in pairwise(channel_list)])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        for lin in self.lins[:-1]:
-            x = F.dropout(F.elu(lin(x)), self.dropout, self.training)
-        return self.lins[-1](x)
+        raise NotImplementedError("DRGNet's MLP holds parameters only; the head runs in "
+                                  "ops.drgnet_head (HIP)")
 
 
 class DRGNet(nn.Module):
@@ -63,6 +69,11 @@ class DRGNet(nn.Module):
         if dense_dim <= 0:
             raise ValueError(f"sortpool_k={sortpool_k} leaves no positions for conv2 (need >= 10)")
         self.mlp = MLP([dense_dim, 128, num_classes], dropout=dropout)
+        self.k = int(sortpool_k)
+        self.dropout = float(dropout)
+        self._dropout_key = repr(self.dropout)
+        # the head's dropout generator (lesion_gnn_amd.dropout; not in state_dict)
+        self.register_buffer("_dropout_rng", dropout_state(self), persistent=False)
 
     def forward(self, x: torch.Tensor, edge_index, batch: torch.Tensor,
                 edge_weight: torch.Tensor | None = None,
@@ -70,13 +81,17 @@ class DRGNet(nn.Module):
         g = as_graph(edge_index, x.size(0), batch, num_graphs)
         xs = []
         for conv in self.graph_convs:
-            x = F.elu(conv(x, g, edge_weight))
+            x = conv(x, g, edge_weight, elu=True)  # ELU(rel + root) as one HIP launch
             xs.append(x)
         x = self.sort_pool(torch.cat(xs, dim=1), graph=g)  # [B, k * (h * L + 1)]
-        x = x.unsqueeze(1)
-        x = self.max_pool(F.elu(self.conv1(x)))
-        x = F.elu(self.conv2(x))
-        return self.mlp(x.view(x.size(0), -1))
+        lin0, lin1 = self.mlp.lins
+        mask = None
+        if self.training and self.dropout > 0.0:  # one launch; the counter advances by one
+            mask = lgnn_dropout.masks(self._dropout_rng, [(x.size(0), lin0.out_features)],
+                                      lgnn_dropout.key(self, self.dropout))[0]
+        return ops.drgnet_head(x, self.k, self.conv1.weight, self.conv1.bias, self.conv2.weight,
+                               self.conv2.bias, lin0.weight, lin0.bias, lin1.weight, lin1.bias,
+                               mask)
 
 
 @dataclasses.dataclass(kw_only=True)

@@ -2276,6 +2276,177 @@ def sort_pool(x, graph: Graph, k: int):
     return _SortPool.apply(x, graph, k)
 
 
+def add_act_fwd(a, b):
+    """ELU(a + b) on lgnn_add_act."""
+    _lib.require_gpu(a, b)
+    a, b = _f32c(a), _f32c(b)
+    if a.shape != b.shape:
+        raise ValueError(f"add_elu: shapes differ, {tuple(a.shape)} and {tuple(b.shape)}")
+    y = torch.empty_like(a)
+    _lib.call("lgnn_add_act", a, b, y, a.numel(), _lib.LGNN_ACT_ELU, _s(a.device))
+    return y
+
+
+def add_act_bwd(dy, y):
+    """dZ = dy * ELU'(y) from the saved output (lgnn_act_bwd): the gradient of both summands."""
+    dy = _f32c(dy)
+    dz = torch.empty_like(dy)
+    _lib.call("lgnn_act_bwd", dy, y, dz, dy.numel(), _lib.LGNN_ACT_ELU, _s(dy.device))
+    return dz
+
+
+class _AddElu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        y = add_act_fwd(a, b)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dz = add_act_bwd(dy, ctx.saved_tensors[0])
+        return dz, dz
+
+
+def add_elu(a, b):
+    """ELU(a + b) as one HIP launch, forward and backward (GraphConv's two branches and the
+    activation after it): the same kernel eager and compiled."""
+    if _compiling():
+        _lgnn()
+        return torch.ops.lgnn.add_elu(a, b)
+    return _AddElu.apply(a, b)
+
+
+# ----------------------------------------------------------------------------------------------
+# DRGNet head: Conv1d / ELU / MaxPool1d / Conv1d / ELU / Lin / ELU / dropout / Lin
+# ----------------------------------------------------------------------------------------------
+
+
+DrgHeadSaved = namedtuple("DrgHeadSaved", "x k params mask a1 sel a2 h")
+
+# the envelope of lgnn_drgnet_head_fwd / _bwd (include/lgnn.h)
+_HEAD_LIMITS = {"D": (1, 4097), "k": (10, 512), "c0": (1, 64), "c1": (1, 64), "H": (1, 256),
+                "C": (1, 16)}
+
+
+def drgnet_head_dims(x, k, params, mask=None) -> tuple:
+    """(B, D, c0, c1, H, dense, C) of a head call, every shape checked against k and
+    D = x.size(1) // k and against the kernels' limits (ValueError naming what is off)."""
+    w1, b1, w2, b2, l0w, l0b, l1w, l1b = params
+    k = int(k)
+    if x.dim() != 2 or k < 1 or x.size(1) % k != 0 or x.size(1) == 0:
+        raise ValueError(f"drgnet_head: x must be [B, k * D] with k = {k}, got "
+                         f"{tuple(x.shape)}")
+    B, D = x.size(0), x.size(1) // k
+    if w1.dim() != 3 or w1.size(1) != 1 or w1.size(2) != D:
+        raise ValueError(f"drgnet_head: conv1.weight must be [c0, 1, D = {D}], got "
+                         f"{tuple(w1.shape)}")
+    c0 = w1.size(0)
+    if w2.dim() != 3 or w2.size(1) != c0 or w2.size(2) != 5:
+        raise ValueError(f"drgnet_head: conv2.weight must be [c1, c0 = {c0}, 5], got "
+                         f"{tuple(w2.shape)}")
+    c1 = w2.size(0)
+    dense = c1 * (k // 2 - 4)
+    if l0w.dim() != 2 or l0w.size(1) != dense:
+        raise ValueError(f"drgnet_head: lins.0.weight must be [H, c1 * (k // 2 - 4) = {dense}], "
+                         f"got {tuple(l0w.shape)}")
+    H = l0w.size(0)
+    if l1w.dim() != 2 or l1w.size(1) != H:
+        raise ValueError(f"drgnet_head: lins.1.weight must be [C, H = {H}], got "
+                         f"{tuple(l1w.shape)}")
+    C = l1w.size(0)
+    for name, b, n in (("conv1", b1, c0), ("conv2", b2, c1), ("lins.0", l0b, H),
+                       ("lins.1", l1b, C)):
+        if tuple(b.shape) != (n,):
+            raise ValueError(f"drgnet_head: {name}.bias must be [{n}], got {tuple(b.shape)}")
+    if mask is not None and tuple(mask.shape) != (B, H):
+        raise ValueError(f"drgnet_head: mask must be [B, H] = [{B}, {H}], got "
+                         f"{tuple(mask.shape)}")
+    if not torch.compiler.is_compiling():  # under a trace B and the widths may be symbolic
+        for name, v in (("D", D), ("k", k), ("c0", c0), ("c1", c1), ("H", H), ("C", C)):
+            lo, hi = _HEAD_LIMITS[name]
+            if not lo <= v <= hi:
+                raise ValueError(f"drgnet_head: {name} = {v} is outside the kernels' limit "
+                                 f"{lo} <= {name} <= {hi}")
+        if B < 1:
+            raise ValueError("drgnet_head: B = 0 graphs (the kernels take B >= 1)")
+        if (B + 64) * max(dense, H + H % 2) >= 2 ** 29:
+            raise ValueError(f"drgnet_head: B = {B} is outside the kernels' limit "
+                             "(B + 64) * max(dense, H) < 2^29")
+    return B, D, c0, c1, H, dense, C
+
+
+def drgnet_head_fwd(x, k, params, mask=None):
+    """The DRGNet head after SortAggregation (reference drgnet.py:60-64) on lgnn_drgnet_head_fwd:
+    (logits [B, C], DrgHeadSaved). params: conv1.weight / bias, conv2.weight / bias,
+    lins.0.weight / bias, lins.1.weight / bias; mask: the dropout mask [B, H] or None."""
+    B, D, c0, c1, H, dense, C = drgnet_head_dims(x, k, params, mask)
+    _lib.require_gpu(x, *params, mask)
+    x = _f32c(x)
+    params = tuple(_f32c(p) for p in params)
+    mask = _f32c(mask) if mask is not None else None
+    dev, K2 = x.device, int(k) // 2
+    f32 = dict(dtype=torch.float32, device=dev)
+    logits = torch.empty(B, C, **f32)
+    a1 = torch.empty(B, K2, c0, **f32)
+    sel = torch.empty(B, K2, (c0 + 15) // 16, dtype=torch.int16, device=dev)
+    a2 = torch.empty(B, dense, **f32)
+    h = torch.empty(B, H, **f32)
+    w1, b1, w2, b2, l0w, l0b, l1w, l1b = params
+    _lib.call("lgnn_drgnet_head_fwd", x, B, int(k), D, w1, b1, c0, w2, b2, c1, l0w, l0b, H, dense,
+              l1w, l1b, C, mask, logits, a1, sel, a2, h, _s(dev))
+    return logits, DrgHeadSaved(x, int(k), params, mask, a1, sel, a2, h)
+
+
+def drgnet_head_bwd(sv: DrgHeadSaved, dlogits):
+    """(dx, [the eight parameter gradients in DrgHeadSaved.params order]) on lgnn_drgnet_head_bwd:
+    three launches, no atomics, bitwise reproducible."""
+    w1, _, w2, _, l0w, _, l1w, _ = sv.params
+    B, D = sv.x.size(0), sv.x.size(1) // sv.k
+    c0, c1, (H, dense), C = w1.size(0), w2.size(0), l0w.shape, l1w.size(0)
+    He = H + H % 2
+    dev = sv.x.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    nws = _lib.query("lgnn_drgnet_head_workspace_bytes", B, sv.k, D, c0, c1, H, C)
+    if nws == 0:
+        raise ValueError("drgnet_head: shape outside the kernels' limits")
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    dx = torch.empty_like(sv.x)
+    dh = torch.empty(B, He, **f32)
+    dw1, db1 = torch.empty_like(w1), torch.empty(c0, **f32)
+    dw2, db2 = torch.empty_like(w2), torch.empty(c1, **f32)
+    dl0w, dl0b = torch.empty(He, dense, **f32), torch.empty(He, **f32)
+    dl1w, dl1b = torch.empty_like(l1w), torch.empty(C, **f32)
+    _lib.call("lgnn_drgnet_head_bwd", _f32c(dlogits), sv.x, B, sv.k, D, w1, c0, w2, c1, l0w, H,
+              dense, l1w, C, sv.mask, sv.a1, sv.sel, sv.a2, sv.h, dx, dh, dw1, db1, dw2, db2,
+              dl0w, dl0b, dl1w, dl1b, ws, nws, _s(dev))
+    return dx, [dw1, db1, dw2, db2, dl0w[:H], dl0b[:H], dl1w, dl1b]
+
+
+class _DrgnetHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, k, mask, *params):
+        logits, saved = drgnet_head_fwd(x, k, params, mask)
+        _save(ctx, saved)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        dx, dparams = drgnet_head_bwd(_load(ctx), dlogits)
+        return (dx, None, None, *dparams)
+
+
+def drgnet_head(x, k, conv1_w, conv1_b, conv2_w, conv2_b, lin0_w, lin0_b, lin1_w, lin1_b,
+                mask=None):
+    """DRGNet's head on the sort-pooled x [B, k * D]: logits [B, C], with gradients for x and the
+    eight parameters (none for the mask). HIP only: no torch route."""
+    params = (conv1_w, conv1_b, conv2_w, conv2_b, lin0_w, lin0_b, lin1_w, lin1_b)
+    if _compiling():
+        _lgnn()
+        return torch.ops.lgnn.drgnet_head(x, int(k), list(params), mask)[0]
+    return _DrgnetHead.apply(x, k, mask, *params)
+
+
 def cc_pool(features: torch.Tensor, cc: torch.Tensor, num_segments: int, reduce_max: bool,
             validate: bool = True) -> torch.Tensor:
     """features (C, P) fp32 channel-major, cc (P,) int64 -> (num_segments, C): per-label mean or
