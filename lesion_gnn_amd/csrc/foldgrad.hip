@@ -13,11 +13,12 @@
 
 namespace {
 
-constexpr int FT = 256;      // threads: 128 output columns x 2 groups of 4 rows
-constexpr int FR = 8;        // output rows per workgroup
+constexpr int FT = 256;      // threads: 128 output columns x FR rows
+constexpr int FR = 2;        // output rows per workgroup: one output element per thread
 constexpr int FW = 128;      // widest layer
 constexpr int FLD = FW + 4;  // padded row of the W_0 image (16-B reads of consecutive rows spread
                              // over the banks)
+static_assert(FT == FW * FR, "one thread per output element");
 
 struct FoldArgs {
   const float* T;   // [w2][d_in]
@@ -62,23 +63,26 @@ __device__ __forceinline__ void copy_store(float* dst, int ld, const f32x4 (&v)[
   }
 }
 
-// workgroups [0, ceil(w1 / 8)): rows i0.. of dW_0 (and db_0); the rest: rows n0.. of dW_1.
-// The launch is latency bound, so everything a workgroup reads from global memory is issued up
-// front, the 64 KiB operand first: one memory round trip. live (nullable): the closed-tile count
-// of the backward launch; 0 = T and g are zero (and were not reduced): only the open totals.
+// workgroups [0, ceil(w1 / 2)): rows i0.. of dW_0 (and db_0); the rest: rows n0.. of dW_1; 128
+// workgroups at the full widths. The launch is latency bound and every output element is one
+// dependent chain, so the rows are spread thin: 2 per workgroup, one element per thread (8 rows
+// as 4 chains per thread on 32 workgroups took 9.2 us). Everything a workgroup reads from
+// global memory is issued up front, the 64 KiB operand first: one memory round trip. live
+// (nullable): the closed-tile count of the backward launch; 0 = T and g are zero (and were not
+// reduced): only the open totals.
 __global__ __launch_bounds__(FT) void k_fold_wgrad(FoldArgs a) {
   __shared__ __attribute__((aligned(16))) float big[FW * FLD];  // T, or the padded W_0 image
-  __shared__ __attribute__((aligned(16))) float strip[FW * FR];  // W_1 columns / T rows
+  __shared__ __attribute__((aligned(16))) float strip[FR * FW];  // W_1 columns / T rows, [FR][FW]
   __shared__ float gs[FW];
   const int t = threadIdx.x;
   const int c = t & (FW - 1), rg = t >> 7;
   const int d_in = a.d_in, w1 = a.w1, w2 = a.w2;
   const int nb0 = (w1 + FR - 1) / FR;
   const int q = d_in / 4;  // 16-B pieces per row of T and W_0
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   const bool role0 = (int)blockIdx.x < nb0;
   const int r0 = FR * (role0 ? (int)blockIdx.x : (int)blockIdx.x - nb0);  // first output row
   const int rows = role0 ? w1 : w2, cols = role0 ? d_in : w1;             // of the output
+  const int r = r0 + rg;                                                  // this thread's row
   float* const out = role0 ? a.dW0 : a.dW1;
   const float* const open = role0 ? a.dW0_open : a.dW1_open;
   // (issued whether alive or not: the live word's own round trip is not waited for first)
@@ -88,34 +92,29 @@ __global__ __launch_bounds__(FT) void k_fold_wgrad(FoldArgs a) {
   // dead, and the open totals are the outputs themselves (as the training step passes them):
   // they are the result already. The workgroup ends with its operand loads still in flight
   if (!alive && open == out && (!role0 || a.db0_open == a.db0)) return;
-  // this thread's 4 open totals (rows r0 + 4 rg + j, column c), db_0's, g, b_0
-  float ov[4] = {0.f, 0.f, 0.f, 0.f};
-  if (open && c < cols) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (r0 + 4 * rg + j < rows) ov[j] = open[(int64_t)(r0 + 4 * rg + j) * cols + c];
-  }
+  // this thread's open total (row r, column c), db_0's, g, b_0
+  const float ov = (open && c < cols && r < rows) ? open[(int64_t)r * cols + c] : 0.f;
   const bool dbt = role0 && t < FR && r0 + t < w1;  // this thread forms db_0[r0 + t]
   const float obv = (a.db0_open && dbt) ? a.db0_open[r0 + t] : 0.f;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  float acc = 0.f;
   double dbs = 0.0;
   if (alive) {
     const float gv = t < w2 ? a.g[t] : 0.f;
     if (role0) {
-      // W_1's columns r0..r0+7 as [n][8] (FT / 2 = FW rows); T whole ([w2][d_in], dense)
-      const int sn = t >> 1, si = r0 + 4 * (t & 1);
-      const f32x4 sv = (sn < w2 && si < w1) ? ld4(a.W1 + (int64_t)sn * w1 + si) : z;
+      // W_1's columns r0, r0 + 1 as [2][n] (thread t: row t / 2, column t % 2: 8 bytes of a
+      // row from a lane pair); T whole ([w2][d_in], dense)
+      const int sn = t >> 1, si = r0 + (t & 1);
+      const float sv = (sn < w2 && si < w1) ? a.W1[(int64_t)sn * w1 + si] : 0.f;
       copy_store(big, d_in, v, w2 * q, q);
-      st4(strip + FR * sn + 4 * (t & 1), sv);
+      strip[FW * (t & 1) + sn] = sv;
       if (t < FW) gs[t] = gv;
       __syncthreads();
       const int kc = c < d_in ? c : 0;
-#pragma unroll 8
-      for (int n = 0; n < w2; ++n) {
-        const float tv = big[n * d_in + kc];
-        const f32x4 wv = ld4(strip + FR * n + 4 * rg);
+#pragma unroll 2
+      for (int n = 0; n < w2; n += 4) {  // w2 % 4 == 0
+        const f32x4 wv = ld4(strip + FW * rg + n);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = fmaf(wv[j], tv, acc[j]);
+        for (int e = 0; e < 4; ++e) acc = fmaf(wv[e], big[(n + e) * d_in + kc], acc);
       }
       if (dbt) {
         // db_0 sums w2 products of mixed sign whose total is far below their magnitudes (g is a
@@ -123,16 +122,17 @@ __global__ __launch_bounds__(FT) void k_fold_wgrad(FoldArgs a) {
         // the only rounding left is g's own and the final one. Four interleaved chains, n mod 4,
         // combined in a fixed order: the latency of one
         double s4[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int n = 0; n < w2; n += 4) {  // w2 % 4 == 0
+        for (int n = 0; n < w2; n += 4) {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            s4[e] = fma((double)strip[FR * (n + e) + t], (double)gs[n + e], s4[e]);
+            s4[e] = fma((double)strip[FW * t + n + e], (double)gs[n + e], s4[e]);
         }
         dbs = (s4[0] + s4[1]) + (s4[2] + s4[3]);
       }
     } else {
-      // T's rows r0..r0+7 as [8][128] (FR q <= FT pieces), b_0; W_0 ([w1][d_in]) as padded rows
+      // T's rows r0, r0 + 1 as [2][128] (FR q <= 64 pieces), b_0; W_0 ([w1][d_in]) as padded rows
       const int sr = t / q, sp = t - sr * q;
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       const f32x4 sv =
           (sr < FR && r0 + sr < w2) ? ld4(a.T + (int64_t)(r0 + sr) * d_in + 4 * sp) : z;
       const float bv = c < w1 ? a.b0[c] : 0.f;
@@ -144,24 +144,14 @@ __global__ __launch_bounds__(FT) void k_fold_wgrad(FoldArgs a) {
 #pragma unroll 4
       for (int p = 0; p < q; ++p) {
         const f32x4 wv = ld4(big + ic * FLD + 4 * p);
+        const f32x4 tv = ld4(strip + FW * rg + 4 * p);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x4 tv = ld4(strip + FW * (4 * rg + j) + 4 * p);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc[j] = fmaf(tv[e], wv[e], acc[j]);
-        }
+        for (int e = 0; e < 4; ++e) acc = fmaf(tv[e], wv[e], acc);
       }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] = fmaf(gs[(r0 + 4 * rg + j) & (FW - 1)], bv, acc[j]);
+      acc = fmaf(gs[r & (FW - 1)], bv, acc);
     }
   }
-  if (c < cols) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = r0 + 4 * rg + j;
-      if (r < rows) out[(int64_t)r * cols + c] = open ? acc[j] + ov[j] : acc[j];
-    }
-  }
+  if (c < cols && r < rows) out[(int64_t)r * cols + c] = open ? acc + ov : acc;
   if (dbt) a.db0[r0 + t] = (float)(a.db0_open ? dbs + (double)obv : dbs);
 }
 

@@ -145,11 +145,16 @@ __device__ __forceinline__ void prep_body(int32_t* __restrict__ zero, int64_t nz
   }
 }
 
-// workgroups past the build's own grid (gx) run the weight-plane side job (lgnn_graph_build_planes)
+// the first plane_blocks(pj) workgroups of a build's first launch run the weight-plane side job
+// (lgnn_graph_build_planes), ahead of the build's own gx: the fold slot's fetch of the weights
+// is the launch's longest wait, so it starts first
 static_assert(kThreads == lgnn_s3::FOLD_NT, "the fold slot is run by whole 256-thread workgroups");
-__device__ __forceinline__ bool plane_side_job(const lgnn_s3::PlaneArgs& pj, int gx) {
-  if ((int)blockIdx.x < gx) return false;
-  lgnn_s3::wplanes_item(pj, ((int)blockIdx.x - gx) * kThreads + threadIdx.x);
+__host__ __device__ inline int plane_blocks(const lgnn_s3::PlaneArgs& pj) {
+  return (lgnn_s3::plane_items(pj) + kThreads - 1) / kThreads;
+}
+__device__ __forceinline__ bool plane_side_job(const lgnn_s3::PlaneArgs& pj) {
+  if ((int)blockIdx.x >= plane_blocks(pj)) return false;
+  lgnn_s3::wplanes_item(pj, (int)blockIdx.x * kThreads + threadIdx.x);
   return true;
 }
 
@@ -159,8 +164,9 @@ __global__ __launch_bounds__(kThreads) void k_prep(int32_t* __restrict__ zero, i
                                                    const int64_t* __restrict__ batch, int64_t M,
                                                    int64_t B, int32_t* __restrict__ gptr,
                                                    lgnn_s3::PlaneArgs pj, int gx) {
-  if (plane_side_job(pj, gx)) return;
-  prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr, blockIdx.x, gx);
+  if (plane_side_job(pj)) return;
+  prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr,
+            (int)blockIdx.x - plane_blocks(pj), gx);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -204,14 +210,15 @@ __global__ __launch_bounds__(kThreads) void k_prep_sorted(int32_t* __restrict__ 
                                                           int32_t* __restrict__ gptr,
                                                           SortedArgs a, lgnn_s3::PlaneArgs pj,
                                                           int gx) {
-  if (plane_side_job(pj, gx)) return;  // (block-uniform: before any barrier)
+  if (plane_side_job(pj)) return;  // (block-uniform: before any barrier)
+  const int bx = (int)blockIdx.x - plane_blocks(pj);  // among the build's own gx workgroups
   constexpr int CH = kSortedChunks;
   const int64_t E = a.E, N = M;
   const int64_t* __restrict__ src = a.ei;
   const int64_t* __restrict__ dst = a.ei + E;
   const bool drop_loops = a.loops != LGNN_LOOPS_KEEP;
   const int lane = threadIdx.x & 63;
-  const int64_t wv = ((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6;
+  const int64_t wv = ((int64_t)bx * kThreads + threadIdx.x) >> 6;
   const int64_t nwv = ((int64_t)gx * kThreads) >> 6;
   int bad = 0;
   bool prepped = false;
@@ -228,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void k_prep_sorted(int32_t* __restrict__ 
     }
     const int64_t before = base > 0 ? dst[base - 1] : -1;
     if (!prepped) {
-      prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr, blockIdx.x, gx);
+      prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr, bx, gx);
       prepped = true;
     }
 #pragma unroll
@@ -294,11 +301,11 @@ __global__ __launch_bounds__(kThreads) void k_prep_sorted(int32_t* __restrict__ 
       }
     }
   }
-  if (!prepped) prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr, blockIdx.x, gx);
+  if (!prepped) prep_body(zero, nzero, tile_open, ntiles, batch, M, B, gptr, bx, gx);
   const int b1 = __syncthreads_or(bad & 1), b2 = __syncthreads_or(bad & 2);
   const int b4 = __syncthreads_or(bad & 4), b8 = __syncthreads_or(bad & 8);
   if (threadIdx.x == 0)
-    a.verdict[blockIdx.x] = (b1 ? 1 : 0) | (b2 ? 2 : 0) | (b4 ? 4 : 0) | (b8 ? 8 : 0);
+    a.verdict[bx] = (b1 ? 1 : 0) | (b2 ? 2 : 0) | (b4 ? 4 : 0) | (b8 ? 8 : 0);
 }
 
 // The build mode from k_prep_sorted's verdict words (block-uniform, every thread must call it):
@@ -1165,8 +1172,7 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
   // the weight-plane side job rides the first launch as extra workgroups
   lgnn_s3::PlaneArgs pj{};
   if (planes) pj = *planes;
-  const int pblocks =
-      planes ? (lgnn_s3::plane_items(pj) + kThreads - 1) / kThreads : 0;
+  const int pblocks = plane_blocks(pj);  // (0 without a job)
   // target-sorted fast path: only for builds without the source CSR (or lazily with it) and
   // without tmap
   SortedArgs sa{};

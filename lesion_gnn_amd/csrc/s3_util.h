@@ -130,9 +130,10 @@ __device__ __forceinline__ int frag_index(int row, int phys) {
 //   Wp[l][plane][n / 32][s][h][n % 32][8]  holds  phys positions 16 s + 8 h .. + 7 of row n
 // (lane h * 32 + n % 32 of wave n / 32 loads k-step s with one 16-B load). With WpT also the
 // transposed planes (rows k, positions perm16(n)) in the same order: the backward's dH = G W_l
-// operand. Item i = one (slot, n, 4 consecutive k), plane_items() in all: the nl layers' and, with
-// b0, the fold slot's (W_10 = W_1 W_0, its fp32 b_10 behind it). Run by
-// k_wplanes (stack3.hip) or as side work of the graph build's first launch (graph.hip).
+// operand. plane_items() items in all: with b0 first the fold slot's (W_10 = W_1 W_0, its fp32
+// b_10 behind its planes), one (n, k) each, then the nl layers', one (layer, n, 4 consecutive k)
+// each. Run by k_wplanes (stack3.hip) or as side work of the graph build's first launch
+// (graph.hip).
 struct PlaneArgs {
   const float* W[LGNN_MAX_STACK];
   int N[LGNN_MAX_STACK];
@@ -143,85 +144,123 @@ struct PlaneArgs {
   const float* b0;  // fold slot (LGNN_PLANE_JOB_FOLD): in_proj's bias; nullptr = no fold slot
 };
 constexpr int PLANE_ITEMS = WP * WP / 4;  // items per layer
-// items of the job: the layers' and, with the fold, the fold slot's
+constexpr int FOLD_ITEMS = WP * WP;       // items of the fold slot
+constexpr int FOLD_NT = 256;  // threads per workgroup of every kernel that runs the job
+static_assert(PLANE_ITEMS % FOLD_NT == 0 && FOLD_ITEMS % FOLD_NT == 0,
+              "every slot is whole workgroups: the slot test is block-uniform");
+// items of the job: the fold slot's (first: its workgroups fetch the most) and the layers'
 __host__ __device__ inline int plane_items(const PlaneArgs& a) {
-  return (a.nl + (a.b0 ? 1 : 0)) * PLANE_ITEMS;
+  return (a.b0 ? FOLD_ITEMS : 0) + a.nl * PLANE_ITEMS;
 }
 // the fold slot's fp32 b_10 [WP], behind its planes
 __host__ __device__ inline float* fold_bias(uint16_t* Wp, int nl) {
   return reinterpret_cast<float*>(Wp + (size_t)(nl + 1) * 3 * PLANE);
 }
 
-// Fold slot, item (n, 4 consecutive k): W_10 = W_1 W_0 (in_proj folded into conv 1, exact: no
-// activation between them), W_10[n][k..k+3] = sum_j W_1[n][j] W_0[j][k..k+3] in fp32 fmaf, j
-// ascending (a fixed order: the same bits from every launch that runs the job), split like any
-// other slot; the k == 0 items also write b_10[n] = sum_j W_1[n][j] b_0[j] as fp32 behind it.
-// Run by whole 256-thread workgroups (a slot's items start at a multiple of 256: the slot test
-// is block-uniform), 8 rows n each. The sums are 128 terms long, so nothing is loaded inside
-// them: the workgroup's 8 rows of W_1, b_0 and W_0 (two halves of 64 rows, 36.5 KiB of LDS in
-// all) are fetched by loads that are all in flight at once, each element once per workgroup, and
-// the fmaf chains read LDS. (A global load per term costs a memory round trip per term and
-// every W_0 element is wanted by 128 rows: that form held the build's first launch for 25 us.)
-constexpr int FOLD_NT = 256;   // threads per workgroup of every kernel that runs the job
-constexpr int FOLD_HALF = 64;  // rows of W_0 staged at a time
+// Fold slot, item (n, k): W_10 = W_1 W_0 (in_proj folded into conv 1, exact: no activation
+// between them), W_10[n][k] = sum_j W_1[n][j] W_0[j][k] in fp32 fmaf, j ascending (a fixed
+// order: the same bits from every launch that runs the job), split like any other slot; every
+// thread also runs b_10[n] = sum_j W_1[n][j] b_0[j] ahead of it (while its loads are in flight)
+// and the k == 0 item writes it as fp32 behind the planes. Run by whole 256-thread
+// workgroups, 2 rows n each (64 workgroups: the sums are the launch's longest dependent chains,
+// so they are spread thin). The sums are up to 128 terms long, so no term waits for a load of
+// its own: a thread fetches its column k of W_0 straight into registers (consecutive lanes,
+// consecutive k: 256 B per wave and row), rows 0..63 all in flight before the first fmaf (as
+// many as a wave can have outstanding) and row j + 64 into the register term j has just left,
+// 64 terms ahead of its use; the workgroup's 2 rows of W_1 and b_0 (1.5 KiB of LDS, fetched
+// ahead of the columns) are read as broadcasts. The build's own workgroups carry the kernel's
+// registers, hence 64 and not 128 of them for the column.
+// (A global load per term costs a memory round trip per term: that form held the build's first
+// launch for 25 us; 8 rows per workgroup with W_0 staged through 32 KiB of LDS for 12 us.)
+constexpr int FOLD_ROWS = FOLD_NT / WP;  // rows of W_10 per workgroup
 struct FoldSmem {
-  float w0[FOLD_HALF][WP];
-  float w1[FOLD_NT / (WP / 4)][WP];
+  float w1[FOLD_ROWS][WP];
   float b0[WP];
 };
 __device__ __forceinline__ void wplanes_fold_item(const PlaneArgs& a, int n, int k) {
   __shared__ __attribute__((aligned(16))) FoldSmem sm;
   const int K = a.K[0], J = a.N[0], N = a.N[1];  // W_0 [J][K], W_1 [N][J]; all multiples of 4
-  // (k = 4 (threadIdx.x % 32), n = the workgroup's first row + threadIdx.x / 32)
-  const int t = threadIdx.x, tr = t / (WP / 4);
-  constexpr int PER = FOLD_HALF * WP / 4 / FOLD_NT;  // float4 of a half per thread
-  // every load up front; what lies past a width is zero, so the padding needs no branch below
-  f32x4 g[2][PER];
+  // (k = threadIdx.x % 128, n = the workgroup's first row + threadIdx.x / 128)
+  const int t = threadIdx.x;
+  // the small operands first (the barrier below waits for them alone): threads 0..63 a 16-B
+  // piece of the 2 rows of W_1, threads 64..95 one of b_0; zero past the widths
+  const int sr = t / (WP / 4), sp = 4 * (t % (WP / 4));
+  f32x4 sv = zero4();
+  if (sr < FOLD_ROWS) {
+    const int sn = n - t / WP + sr;
+    if (sn < N && sp < J) sv = ld4(a.W[1] + (int64_t)sn * J + sp);
+  } else if (sr == FOLD_ROWS) {
+    if (sp < J) sv = ld4(a.b0 + sp);
+  }
+  // column k of W_0 (columns past K: a valid address again, not used): a uniform row pointer
+  // and one lane offset, not a lane address per row
+  constexpr int RING = 64;
+  const unsigned kk = k < K ? k : 0;
+  const float* row = a.W[0];
+  float c0[RING];
 #pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int j = FOLD_HALF * h + tr + (FOLD_NT / (WP / 4)) * u;
-      g[h][u] = (j < J && k < K) ? ld4(a.W[0] + (int64_t)j * K + k) : zero4();
-    }
-  st4(&sm.w1[tr][k], (n < N && k < J) ? ld4(a.W[1] + (int64_t)n * J + k) : zero4());
-  if (t < WP / 4) st4(&sm.b0[k], k < J ? ld4(a.b0 + k) : zero4());
-  f32x4 v = zero4();
+  for (int j = 0; j < RING; ++j) {
+    c0[j] = row[kk];
+    if (j + 1 < J) row += K;  // (rows past J: the last row again, not used)
+  }
+  if (sr < FOLD_ROWS) st4(&sm.w1[sr][sp], sv);
+  else if (sr == FOLD_ROWS) st4(&sm.b0[sp], sv);
+  __syncthreads();
+  const float* w1r = sm.w1[t / WP];
+  // b_10's chain first: it needs the small operands only and runs while the columns arrive
+  // (in one loop with W_10's the two become packed FMAs and c0 takes twice the registers)
   float s = 0.f;
+  for (int j = 0; j < J; j += 4) {
+    const f32x4 c = ld4(w1r + j);
+    const f32x4 bq = ld4(&sm.b0[j]);
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    if (h) __syncthreads();  // the first half is read
+    for (int u = 0; u < 4; ++u) s = fmaf(c[u], bq[u], s);
+  }
+  float v = 0.f;
 #pragma unroll
-    for (int u = 0; u < PER; ++u) st4(&sm.w0[tr + (FOLD_NT / (WP / 4)) * u][k], g[h][u]);
-    __syncthreads();
-    const int je = J - FOLD_HALF * h < FOLD_HALF ? J - FOLD_HALF * h : FOLD_HALF;
-    for (int j = 0; j < je; j += 4) {
-      const f32x4 c = ld4(&sm.w1[tr][FOLD_HALF * h + j]);
-      const f32x4 bq = ld4(&sm.b0[FOLD_HALF * h + j]);
+  for (int j = 0; j < WP; j += 4) {
+    if (j < J) {  // (uniform; no early exit: the loop unrolls, c0 stays in registers)
+      const f32x4 c = ld4(w1r + j);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v = fmaf(c[u], c0[(j + u) % RING], v);
+    }
+    // rows j + 64 .. j + 67, outside the branch (a load inside one makes every wait behind the
+    // join a wait for all loads); past J the last row again, not used
+    if (j + RING < WP) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const f32x4 r = ld4(&sm.w0[j + u][k]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = fmaf(c[u], r[q], v[q]);
-        s = fmaf(c[u], bq[u], s);
+        c0[(j + u) % RING] = row[kk];
+        if (j + u + RING + 1 < J) row += K;
       }
     }
   }
-  u32x2 o[3];
-  split4(v, o);
-  uint16_t* base = a.Wp + (size_t)a.nl * 3 * PLANE;
+  if (k >= K) v = 0.f;  // (rows past N: W_1's row is zero)
+  // four consecutive k meet in the lane of the first: one 8-byte store per plane
+  f32x4 v4;
+  v4[0] = v;
+  v4[1] = __shfl_down(v, 1, 64);
+  v4[2] = __shfl_down(v, 2, 64);
+  v4[3] = __shfl_down(v, 3, 64);
+  if ((k & 3) == 0) {
+    u32x2 o[3];
+    split4(v4, o);
+    uint16_t* base = a.Wp + (size_t)a.nl * 3 * PLANE;
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
-    *reinterpret_cast<u32x2*>(base + p * PLANE + frag_index(n, perm16(k))) = o[p];
+    for (int p = 0; p < 3; ++p)
+      *reinterpret_cast<u32x2*>(base + p * PLANE + frag_index(n, perm16(k))) = o[p];
+  }
   if (k == 0) fold_bias(a.Wp, a.nl)[n] = s;  // (zero past w2)
 }
 static_assert(LGNN_PLANE_JOB_MAX == LGNN_MAX_STACK, "plane job layers");
 
 __device__ __forceinline__ void wplanes_item(const PlaneArgs& a, int i) {
   if (i >= plane_items(a)) return;
+  if (a.b0) {
+    if (i < FOLD_ITEMS) return wplanes_fold_item(a, i / WP, i % WP);
+    i -= FOLD_ITEMS;
+  }
   const int l = i / PLANE_ITEMS;
   const int n = (i / (WP / 4)) % WP, k = 4 * (i % (WP / 4));
-  if (l >= a.nl) return wplanes_fold_item(a, n, k);
   const int N = a.N[l], K = a.K[l];
   const f32x4 v = (n < N && k < K) ? ld4(a.W[l] + (int64_t)n * K + k) : zero4();
   u32x2 o[3];

@@ -57,7 +57,8 @@ namespace lgnn_s3 {
 using namespace lgnn_tile;
 constexpr int S3ABL = LGNN_S3_ABLATE;
 
-// Weight planes (s3_util.h wplanes_item): one thread per (layer, n, 4 consecutive k).
+// Weight planes (s3_util.h wplanes_item): one thread per (n, k) of the fold slot, then one per
+// (layer, n, 4 consecutive k).
 __global__ __launch_bounds__(256) void k_wplanes(PlaneArgs a) {
   wplanes_item(a, blockIdx.x * 256 + threadIdx.x);
 }
