@@ -21,7 +21,7 @@
 // MFMAs run. Blocks map to tiles XCD-contiguously (xcd_block).
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 #include "s3_util.h"
 
 namespace lgnn_bf {
@@ -489,10 +489,7 @@ extern "C" int lgnn_bf16_weight_prep(const float* W, int N, int K, uint16_t* Wb,
   const int Kp = lgnn_bf16_kpad(K), Np = lgnn_bf16_kpad(N);
   const int64_t total = (int64_t)128 * Kp + (WTb ? (int64_t)128 * Np : 0);
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 1024);
-  hipLaunchKernelGGL(k_bf_wprep, dim3(grid), dim3(256), 0, as_stream(stream), W, N, K, Kp, Np, Wb,
-                     WTb);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  return launch(k_bf_wprep, dim3(grid), dim3(256), as_stream(stream), W, N, K, Kp, Np, Wb, WTb);
 }
 
 extern "C" int lgnn_bf16_weight_prep_multi(int n, const float* const* W, const int* N,
@@ -515,9 +512,7 @@ extern "C" int lgnn_bf16_weight_prep_multi(int n, const float* const* W, const i
     const int64_t total = (int64_t)128 * jobs.Kp[j] + (WTb[j] ? (int64_t)128 * jobs.Np[j] : 0);
     jobs.first[j + 1] = jobs.first[j] + (int)std::min<int64_t>((total + 255) / 256, 512);
   }
-  hipLaunchKernelGGL(k_bf_wprep_multi, dim3(jobs.first[n]), dim3(256), 0, as_stream(stream), jobs);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  return launch(k_bf_wprep_multi, dim3(jobs.first[n]), dim3(256), as_stream(stream), jobs);
 }
 
 extern "C" int lgnn_bf16_gemm_att(const void* A, int a_is_f32, int64_t M, int K,
@@ -536,14 +531,13 @@ extern "C" int lgnn_bf16_gemm_att(const void* A, int a_is_f32, int64_t M, int K,
   const int Kp = lgnn_bf16_kpad(K);
   const AttOut att{att_src, att_dst, a_s, a_d, H, C};
   const dim3 grid((unsigned)((M + TM - 1) / TM));
-  if (a_is_f32)  // rounded to bf16 as loaded, as lgnn_bf16_gemm does
-    hipLaunchKernelGGL((k_bf_gemm<true, true, 2, true>), grid, dim3(NT), 0, as_stream(stream), A,
-                       M, K, Wb, Kp, nullptr, N, Y, Yb, nullptr, att);
-  else
-    hipLaunchKernelGGL((k_bf_gemm<false, true, 2, true>), grid, dim3(NT), 0, as_stream(stream), A,
-                       M, K, Wb, Kp, nullptr, N, Y, Yb, nullptr, att);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_OK;
+  // f32 rows are rounded to bf16 as loaded, as lgnn_bf16_gemm does
+  one_of<false, true>(a_is_f32 != 0, [&](auto AF) {
+    r = launch(k_bf_gemm<AF, true, 2, true>, grid, dim3(NT), as_stream(stream), A, M, K, Wb, Kp,
+               nullptr, N, Y, Yb, nullptr, att);
+  });
+  return r;
 }
 
 extern "C" int lgnn_bf16_gemm(const void* A, int a_is_f32, int64_t M, int K, const uint16_t* Wb,
@@ -559,28 +553,21 @@ extern "C" int lgnn_bf16_gemm(const void* A, int a_is_f32, int64_t M, int K, con
   const int Kp = lgnn_bf16_kpad(K), nck = Kp / BK;
   const dim3 grid((unsigned)((M + TM - 1) / TM)), block(NT);
   hipStream_t s = as_stream(stream);
-#define LGNN_BFG(AF, V, NC) \
-  hipLaunchKernelGGL((k_bf_gemm<AF, V, NC>), grid, block, 0, s, A, M, K, Wb, Kp, bias, N, Y, Yb, \
-                     colsum_part)
+  int r = LGNN_OK;
+  auto go = [&](auto AF, auto V, auto NC) {
+    r = launch(k_bf_gemm<AF, V, NC>, grid, block, s, A, M, K, Wb, Kp, bias, N, Y, Yb, colsum_part,
+               AttOut{});
+  };
   // the unrolled bodies: K <= 128 (the GAT layers, dX) and K <= 1088 (the reference in_proj,
   // 1025 input channels); other widths run the generic loop
   const bool v = K % 4 == 0;
-  if (!a_is_f32) {
-    if (nck == 2) LGNN_BFG(false, true, 2);
-    else LGNN_BFG(false, true, 0);
-  } else if (nck == 2) {
-    if (v) LGNN_BFG(true, true, 2);
-    else LGNN_BFG(true, false, 2);
-  } else if (nck == 17) {
-    if (v) LGNN_BFG(true, true, 17);
-    else LGNN_BFG(true, false, 17);
-  } else {
-    if (v) LGNN_BFG(true, true, 0);
-    else LGNN_BFG(true, false, 0);
-  }
-#undef LGNN_BFG
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  if (!a_is_f32)  // bf16 rows: K % 4 == 0 (checked above), and no in_proj body
+    one_of<0, 2>(nck, [&](auto NC) { go(std::false_type{}, std::true_type{}, NC); });
+  else
+    one_of<false, true>(v, [&](auto V) {
+      one_of<0, 2, 17>(nck, [&](auto NC) { go(std::true_type{}, V, NC); });
+    });
+  return r;
 }
 
 // chunks per split: the smallest of 3, 6, 12, 24 that keeps the grid within about 480
@@ -610,22 +597,9 @@ extern "C" int lgnn_bf16_wgrad(const uint16_t* dYb, int N, const void* X, int x_
   const int nkb = lgnn_bf16_kpad(K) / BK, cpb = wg_cpb(M, K);
   const dim3 grid((unsigned)(nkb * num_partials)), block(NT);
   hipStream_t s = as_stream(stream);
-#define LGNN_BFW(XF, C) \
-  hipLaunchKernelGGL((k_bf_wgrad<XF, C>), grid, block, 0, s, dYb, N, X, M, K, nkb, partials)
-#define LGNN_BFW_C(XF)              \
-  switch (cpb) {                    \
-    case 3: LGNN_BFW(XF, 3); break;   \
-    case 6: LGNN_BFW(XF, 6); break;   \
-    case 12: LGNN_BFW(XF, 12); break; \
-    default: LGNN_BFW(XF, 24); break; \
-  }
-  if (x_is_f32) {
-    LGNN_BFW_C(true)
-  } else {
-    LGNN_BFW_C(false)
-  }
-#undef LGNN_BFW_C
-#undef LGNN_BFW
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_OK;
+  one_of<false, true>(x_is_f32 != 0, [&](auto XF) { one_of<24, 3, 6, 12>(cpb, [&](auto CPB) {
+    r = launch(k_bf_wgrad<XF, CPB>, grid, block, s, dYb, N, X, M, K, nkb, partials);
+  }); });
+  return r;
 }

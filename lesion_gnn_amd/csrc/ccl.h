@@ -1,7 +1,7 @@
 // The launches of ccl.hip over B images of one size, shared by the one-image entries (ccl.hip)
 // and the batch entries (ccl_batch.hip). They check nothing: the entries do.
 #pragma once
-#include "common.h"
+#include "launch.h"
 
 namespace lgnn_cclk {
 

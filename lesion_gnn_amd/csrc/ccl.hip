@@ -421,10 +421,8 @@ static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int launch_label_pool(const float* logits, int B, int K, int Hin, int Win, uint8_t* out, int H,
                       int W, hipStream_t s) {
   const int64_t npix = (int64_t)B * H * W;
-  hipLaunchKernelGGL(k_label_pool, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, s, logits, B, K, Hin, Win, out, H, W);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_label_pool, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), s,
+                logits, B, K, Hin, Win, out, H, W);
 }
 
 size_t ccl_workspace_bytes(int B, int H, int W) {
@@ -449,27 +447,20 @@ int launch_ccl(const uint8_t* image, int B, int H, int W, int connectivity, int6
 
   const int nseg = (W + kSeg - 1) / kSeg;
   const dim3 sgrid((unsigned)(((int64_t)rows * nseg + kWaves - 1) / kWaves));
-  hipLaunchKernelGGL(k_ccl_init, sgrid, dim3(kThreads), 0, s, image, rows, W, nseg, parent);
-  LGNN_LAUNCH_CHECK();
-  if (connectivity == 8)
-    hipLaunchKernelGGL(k_ccl_merge<true>, sgrid, dim3(kThreads), 0, s, image, rows, H, W, nseg,
-                       parent);
-  else
-    hipLaunchKernelGGL(k_ccl_merge<false>, sgrid, dim3(kThreads), 0, s, image, rows, H, W, nseg,
-                       parent);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_compress, dim3(nb), dim3(kThreads), 0, s, parent, hw, nbi, blockcount);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_scan, dim3(1), dim3(kScanThreads), 0, s, blockcount, nb, nbi, B,
-                     num_labels, node_ptr);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_rank, dim3(nb), dim3(kThreads), 0, s, parent, hw, nbi, blockcount,
-                     rootlabel);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ccl_label, dim3((unsigned)((npix + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, s, parent, rootlabel, npix, labels);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  if (const int e = launch(k_ccl_init, sgrid, dim3(kThreads), s, image, rows, W, nseg,
+                           parent)) return e;
+  one_of<false, true>(connectivity == 8, [&](auto DIAG) {
+    enqueue(k_ccl_merge<DIAG>, sgrid, dim3(kThreads), s, image, rows, H, W, nseg, parent);
+  });
+  if (const int e = last_error()) return e;
+  if (const int e = launch(k_ccl_compress, dim3(nb), dim3(kThreads), s, parent, hw, nbi,
+                           blockcount)) return e;
+  if (const int e = launch(k_ccl_scan, dim3(1), dim3(kScanThreads), s, blockcount, nb, nbi, B,
+                           num_labels, node_ptr)) return e;
+  if (const int e = launch(k_ccl_rank, dim3(nb), dim3(kThreads), s, parent, hw, nbi, blockcount,
+                           rootlabel)) return e;
+  return launch(k_ccl_label, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), s,
+                parent, rootlabel, npix, labels);
 }
 
 // labels [B, H, W] -> num_rows rows of stats and centroids: the rows of image b start at
@@ -480,18 +471,16 @@ int launch_ccl_stats(const int64_t* labels, int B, int H, int W, const int64_t* 
   const int64_t hw = (int64_t)H * W;
   unsigned long long* sums = reinterpret_cast<unsigned long long*>(centroids);
   const dim3 lgrid((unsigned)((num_rows + kThreads - 1) / kThreads));
-  hipLaunchKernelGGL(k_stats_init, lgrid, dim3(kThreads), 0, s, num_rows, stats, sums, err);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch(k_stats_init, lgrid, dim3(kThreads), s, num_rows, stats, sums,
+                           err)) return e;
   const int64_t chunk = (int64_t)kThreads * kRun;
   const int64_t nchunks = (hw + chunk - 1) / chunk;
   const int gpi = (int)std::min<int64_t>(nchunks, 1024);
   const int chunks = (int)((nchunks + gpi - 1) / gpi);
-  hipLaunchKernelGGL(k_stats_acc, dim3((unsigned)((int64_t)B * gpi)), dim3(kThreads), 0, s,
-                     labels, hw, W, num_rows, chunks, gpi, node_ptr, stats, sums, err);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_stats_finish, lgrid, dim3(kThreads), 0, s, num_rows, stats, centroids);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  if (const int e = launch(k_stats_acc, dim3((unsigned)((int64_t)B * gpi)), dim3(kThreads), s,
+                           labels, hw, W, num_rows, chunks, gpi, node_ptr, stats, sums,
+                           err)) return e;
+  return launch(k_stats_finish, lgrid, dim3(kThreads), s, num_rows, stats, centroids);
 }
 
 }  // namespace lgnn_cclk

@@ -16,7 +16,7 @@
 //              per slice; the last-arriving slice of a channel folds the slices in slice order and
 //              divides by the count (mean). Deterministic: every float sum is in a fixed order
 //              except within one wave's LDS add instruction, whose lane order the hardware fixes.
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace lgnn_ccpool {
@@ -192,17 +192,15 @@ extern "C" int lgnn_cc_pool(const float* features, int channels, int64_t num_pix
   if (e == hipSuccess && ns > 1) e = hipMemsetAsync(arrive, 0, (size_t)channels * sizeof(int32_t), s);
   if (e != hipSuccess) return (int)e;
   const int cblocks = (int)std::min<int64_t>(1024, std::max<int64_t>(1, num_pixels / 4096));
-  hipLaunchKernelGGL(k_cc_count, dim3(cblocks), dim3(kThreads), num_segments * sizeof(int32_t), s,
-                     cc, num_pixels, num_segments, count, lab, err);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch_lds(k_cc_count, dim3(cblocks), dim3(kThreads),
+                               num_segments * sizeof(int32_t), s, cc, num_pixels, num_segments,
+                               count, lab, err)) return e;
   const size_t lds = (size_t)kWaves * num_segments * sizeof(float);
   const dim3 grid((unsigned)((int64_t)channels * ns));
-  if (reduce_max)
-    hipLaunchKernelGGL(k_cc_pool<true>, grid, dim3(kThreads), lds, s, features, lab, num_pixels,
-                       channels, num_segments, ns, count, part, arrive, out);
-  else
-    hipLaunchKernelGGL(k_cc_pool<false>, grid, dim3(kThreads), lds, s, features, lab, num_pixels,
-                       channels, num_segments, ns, count, part, arrive, out);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_OK;
+  one_of<false, true>(reduce_max != 0, [&](auto MAX) {
+    r = launch_lds(k_cc_pool<MAX>, grid, dim3(kThreads), lds, s, features, lab, num_pixels,
+                   channels, num_segments, ns, count, part, arrive, out);
+  });
+  return r;
 }

@@ -25,7 +25,7 @@
 //              float operation has a fixed place in a fixed order, so two calls give the same bits.
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace lgnn_ccresample {
@@ -195,22 +195,6 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-template <bool kMax, bool kIdent, int CH>
-static int launch_pool(size_t lds, dim3 grid, hipStream_t s, const float* feat, int C, int h, int w,
-                       const int16_t* lab, int H, int W, const Tap* taps, const int64_t* node_ptr,
-                       int total, int nmax, int cgroups, const int32_t* count, float* out) {
-  if (lds > kPlainLds) {
-    const hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&k_rs_pool<kMax, kIdent, CH>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL((k_rs_pool<kMax, kIdent, CH>), grid, dim3(kThreads), lds, s, feat, C, h, w,
-                     lab, H, W, taps, node_ptr, total, nmax, cgroups, count, out);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
-}
-
 static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static bool dims_ok(int B, int H, int W) {
@@ -258,11 +242,11 @@ extern "C" int lgnn_cc_pool_resample(const float* features, int batch, int chann
   if (e != hipSuccess) return (int)e;
   const int64_t hw = (int64_t)height * width;
   const int cbi = (int)std::min<int64_t>(64, std::max<int64_t>(1, hw / 4096));
-  hipLaunchKernelGGL(k_rs_count, dim3((unsigned)(batch * cbi)), dim3(kThreads),
+  int r = launch_lds(k_rs_count, dim3((unsigned)(batch * cbi)), dim3(kThreads),
                      max_nodes * sizeof(int32_t), s, labels, hw, cbi, node_ptr, total_nodes,
                      max_nodes, count, lab, err, ident ? nullptr : taps, src_height, src_width,
                      height, width);
-  LGNN_LAUNCH_CHECK();
+  if (r != LGNN_OK) return r;
 
   // four channels share a pixel's label, taps and run bookkeeping where their bins and source
   // maps fit the LDS a launch gets unasked; else one channel, with up to 127 KB of LDS
@@ -271,15 +255,21 @@ extern "C" int lgnn_cc_pool_resample(const float* features, int batch, int chann
   const int ch = four ? 4 : 1, cgroups = (channels + ch - 1) / ch;
   const size_t lds = ch * per_channel;
   const dim3 grid((unsigned)((int64_t)batch * cgroups));
-#define LGNN_RS_POOL(MAX, IDENT, CHN)                                                          \
-  launch_pool<MAX, IDENT, CHN>(lds, grid, s, features, channels, src_height, src_width, lab,   \
-                               height, width, taps, node_ptr, total_nodes, max_nodes, cgroups, \
-                               count, out)
-  if (reduce_max) {
-    if (ident) return four ? LGNN_RS_POOL(true, true, 4) : LGNN_RS_POOL(true, true, 1);
-    return four ? LGNN_RS_POOL(true, false, 4) : LGNN_RS_POOL(true, false, 1);
-  }
-  if (ident) return four ? LGNN_RS_POOL(false, true, 4) : LGNN_RS_POOL(false, true, 1);
-  return four ? LGNN_RS_POOL(false, false, 4) : LGNN_RS_POOL(false, false, 1);
-#undef LGNN_RS_POOL
+  one_of<false, true>(reduce_max != 0, [&](auto MAX) { one_of<false, true>(ident, [&](auto ID) {
+    one_of<1, 4>(ch, [&](auto CH) {
+      constexpr auto kernel = k_rs_pool<MAX, ID, CH>;
+      if (lds > kPlainLds) {
+        const hipError_t e =
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+          r = (int)e;
+          return;
+        }
+      }
+      r = launch_lds(kernel, grid, dim3(kThreads), lds, s, features, channels, src_height,
+                     src_width, lab, height, width, taps, node_ptr, total_nodes, max_nodes,
+                     cgroups, count, out);
+    }); }); });
+  return r;
 }

@@ -23,7 +23,7 @@
 // graphs, or the end of the rows, is done float by float. The grid is sized from out_capacity;
 // the row count is read on the device (out_ptr[num_sel]), and workgroups past it return at once.
 // The last workgroups of the grid do the per-row outputs (out_batch, out_pos), kRows rows each.
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace {
@@ -342,20 +342,16 @@ extern "C" int lgnn_collate(const int64_t* ids, int64_t num_sel, const int64_t* 
   int64_t* delta = static_cast<int64_t*>(workspace);
   if (num_sel > 0) {
     if ((num_sel + kT - 1) / kT > 0x7fffffff) return LGNN_EINVAL;
-    hipLaunchKernelGGL(k_collate_sizes, dim3((unsigned)((num_sel + kT - 1) / kT)), dim3(kT), 0,
-                       as_stream(stream), ids, num_sel, src_ptr, num_src_graphs, y, out_y, out_ptr,
-                       delta);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_collate_sizes, dim3((unsigned)((num_sel + kT - 1) / kT)), dim3(kT),
+                             as_stream(stream), ids, num_sel, src_ptr, num_src_graphs, y, out_y,
+                             out_ptr, delta)) return e;
   }
-  hipLaunchKernelGGL(k_collate_scan, dim3(1), dim3(kScanT), 0, as_stream(stream), num_sel, out_ptr,
-                     delta, out_capacity, err);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch(k_collate_scan, dim3(1), dim3(kScanT), as_stream(stream), num_sel,
+                           out_ptr, delta, out_capacity, err)) return e;
   if (num_sel == 0 || out_capacity == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_collate_gather, dim3((unsigned)(x_blocks + row_blocks)), dim3(kT), 0,
-                     as_stream(stream), x, channels, pos, dims, out_ptr, delta, num_sel, out_x,
-                     out_pos, out_batch, out_capacity, x_blocks);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_collate_gather, dim3((unsigned)(x_blocks + row_blocks)), dim3(kT),
+                as_stream(stream), x, channels, pos, dims, out_ptr, delta, num_sel, out_x, out_pos,
+                out_batch, out_capacity, x_blocks);
 }
 
 extern "C" size_t lgnn_collate_edges_workspace_bytes(int64_t num_sel) {
@@ -385,14 +381,12 @@ extern "C" int lgnn_collate_edges(const int64_t* ids, int64_t num_sel, const int
   int64_t* edelta = static_cast<int64_t*>(workspace);
   int64_t* shift = edelta + num_sel;
   if (num_sel > 0) {
-    hipLaunchKernelGGL(k_collate_edge_sizes, dim3((unsigned)((num_sel + kT - 1) / kT)), dim3(kT),
-                       0, as_stream(stream), ids, num_sel, src_ptr, src_edge_ptr, num_src_graphs,
-                       out_ptr, out_edge_ptr, edelta, shift);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_collate_edge_sizes, dim3((unsigned)((num_sel + kT - 1) / kT)),
+                             dim3(kT), as_stream(stream), ids, num_sel, src_ptr, src_edge_ptr,
+                             num_src_graphs, out_ptr, out_edge_ptr, edelta, shift)) return e;
   }
-  hipLaunchKernelGGL(k_collate_scan, dim3(1), dim3(kScanT), 0, as_stream(stream), num_sel,
-                     out_edge_ptr, edelta, out_capacity, err);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch(k_collate_scan, dim3(1), dim3(kScanT), as_stream(stream), num_sel,
+                           out_edge_ptr, edelta, out_capacity, err)) return e;
   if (num_sel == 0 || out_capacity == 0 || num_src_edges == 0) return LGNN_OK;
   if (edge_weight && weight_bytes == 8)
     hipLaunchKernelGGL(k_collate_edge_gather<uint64_t>, dim3((unsigned)blocks), dim3(kT), 0,
@@ -406,6 +400,5 @@ extern "C" int lgnn_collate_edges(const int64_t* ids, int64_t num_sel, const int
                        static_cast<const uint32_t*>(edge_weight), out_edge_ptr, edelta, shift,
                        num_sel, out_edge_index, static_cast<uint32_t*>(out_edge_weight),
                        out_capacity);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }

@@ -12,12 +12,6 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#define LGNN_LAUNCH_CHECK()                         \
-  do {                                              \
-    hipError_t _e = hipGetLastError();              \
-    if (_e != hipSuccess) return (int)_e;           \
-  } while (0)
-
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // the process-wide path options of lgnn_set_option (include/lgnn.h; defined in graph.hip)

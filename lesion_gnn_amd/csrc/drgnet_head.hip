@@ -32,7 +32,7 @@
 // floats from L2 per pass) are the largest stream.
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace lgnn_drgnet_head {
@@ -567,8 +567,7 @@ extern "C" int lgnn_drgnet_head_fwd(const float* x, int64_t num_graphs, int k, i
     hipLaunchKernelGGL(k_head_fwd<false>, grid, block, lf, s, d, x, conv1_w, conv1_b, conv2_w,
                        conv2_b, lin0_w, lin0_b, lin1_w, lin1_b, mask, logits, a1, sel, a2, h);
   }
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_drgnet_head_bwd(const float* dlogits, const float* x, int64_t num_graphs,
@@ -596,9 +595,9 @@ extern "C" int lgnn_drgnet_head_bwd(const float* dlogits, const float* x, int64_
   hipStream_t s = as_stream(stream);
   if (const int e = raise_lds(&k_head_bwd, lb)) return e;
   const Slabs sl = {ws + L.dW1, ws + L.db1, ws + L.dW2, ws + L.db2, ws + L.dL1, ws + L.dbL1};
-  hipLaunchKernelGGL(k_head_bwd, dim3((unsigned)L.slots), dim3(NT), lb, s, d, dlogits, x, conv1_w,
-                     conv2_w, lin0_w, lin1_w, mask, a1, sel, a2, h, dx, dh, sl);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch_lds(k_head_bwd, dim3((unsigned)L.slots), dim3(NT), lb, s, d, dlogits, x,
+                               conv1_w, conv2_w, lin0_w, lin1_w, mask, a1, sel, a2, h, dx, dh,
+                               sl)) return e;
   // dL0 [He][dense] = dh^T a2 and db0 = colsum dh: the library's weight-gradient GEMM, B in chunks
   if (const int e = lgnn_s3_wgrad(dh, d.He, a2, d.B, d.dense, 3, ws + L.dL0, L.sw, ws + L.db0,
                                   stream))

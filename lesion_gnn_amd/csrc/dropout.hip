@@ -19,7 +19,7 @@
 // the seed and counter; with `advance` the last workgroup to finish (last_workgroup: a two-level
 // ticket) increments the counter, so a captured HIP graph draws fresh masks on every replay
 // (torch's generator does the same for captured dropout).
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -130,9 +130,7 @@ extern "C" int lgnn_add_act(const float* a, const float* b, float* y, int64_t n,
   if (n == 0) return LGNN_OK;
   int64_t nb = (n + kT - 1) / kT;
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(k_add_act, dim3((unsigned)nb), dim3(kT), 0, as_stream(stream), a, b, n, y);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_add_act, dim3((unsigned)nb), dim3(kT), as_stream(stream), a, b, n, y);
 }
 
 extern "C" int lgnn_act_bwd(const float* dy, const float* h, float* dz, int64_t n, int act,
@@ -142,9 +140,7 @@ extern "C" int lgnn_act_bwd(const float* dy, const float* h, float* dz, int64_t 
   if (n == 0) return LGNN_OK;
   int64_t nb = (n + 4 * kT - 1) / (4 * kT);
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(k_act_bwd, dim3((unsigned)nb), dim3(kT), 0, as_stream(stream), dy, h, dz, n);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_act_bwd, dim3((unsigned)nb), dim3(kT), as_stream(stream), dy, h, dz, n);
 }
 
 extern "C" int lgnn_dropout_masks(int num_masks, float* const* out, const int64_t* numel,
@@ -172,10 +168,8 @@ extern "C" int lgnn_dropout_masks(int num_masks, float* const* out, const int64_
     const int64_t nb = (numel[i] + per - 1) / per;
     J.boff[i + 1] = J.boff[i] + (int)(nb > 0 ? nb : 1);
   }
-  hipLaunchKernelGGL(k_masks, dim3((unsigned)J.boff[num_masks]), dim3(kT), 0, as_stream(stream), J,
-                     state, advance);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_masks, dim3((unsigned)J.boff[num_masks]), dim3(kT), as_stream(stream), J, state,
+                advance);
 }
 
 extern "C" int lgnn_mask_mul(const float* x, const float* mask, float* y, int64_t n,
@@ -185,8 +179,5 @@ extern "C" int lgnn_mask_mul(const float* x, const float* mask, float* y, int64_
   if (n == 0) return LGNN_OK;
   int64_t nb = (n + 4 * kT - 1) / (4 * kT);
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)nb), dim3(kT), 0, as_stream(stream), x, mask, y,
-                     n);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_mask_mul, dim3((unsigned)nb), dim3(kT), as_stream(stream), x, mask, y, n);
 }

@@ -12,7 +12,7 @@
 //
 // HBM-bound gather: per edge 16 B of indices + 2 * dims * sizeof(pos) of (L2-resident) positions
 // in, 4 or 8 B out. One thread per edge, grid-stride; edge_index rows are read coalesced.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256) void k_gauss(const T* __restrict__ pos, int64_
 }
 
 template <typename T>
-int launch(const T* pos, int64_t n, int dims, const int64_t* ei, int64_t E, double sigma,
-           void* out, int out_f64, int32_t* err, hipStream_t s) {
+int gauss_launch(const T* pos, int64_t n, int dims, const int64_t* ei, int64_t E, double sigma,
+                 void* out, int out_f64, int32_t* err, hipStream_t s) {
   // The two constants are rounded exactly as Python evaluates the reference's expressions in
   // double and torch then rounds the scalar operand to T: `2 * self.sigma**2` (:57) is
   // 2 * (sigma * sigma), and `math.sqrt(2 * math.pi * sigma**2)` (:45) is
@@ -95,8 +95,7 @@ int launch(const T* pos, int64_t n, int dims, const int64_t* ei, int64_t E, doub
   else
     k_gauss<T, float><<<grid, 256, 0, s>>>(pos, n, dims, ei, E, two_s2, norm,
                                            static_cast<float*>(out), err);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 }  // namespace
@@ -110,8 +109,8 @@ extern "C" int lgnn_gaussian_distance(const void* pos, int pos_f64, int64_t num_
   if (hipMemsetAsync(err, 0, sizeof(int32_t), s) != hipSuccess) return LGNN_EINVAL;
   if (num_edges == 0) return LGNN_OK;
   if (!pos || !edge_index || !out) return LGNN_EINVAL;
-  return pos_f64 ? launch(static_cast<const double*>(pos), num_nodes, dims, edge_index,
-                          num_edges, sigma, out, out_f64, err, s)
-                 : launch(static_cast<const float*>(pos), num_nodes, dims, edge_index, num_edges,
-                          sigma, out, out_f64, err, s);
+  return pos_f64 ? gauss_launch(static_cast<const double*>(pos), num_nodes, dims, edge_index,
+                                num_edges, sigma, out, out_f64, err, s)
+                 : gauss_launch(static_cast<const float*>(pos), num_nodes, dims, edge_index,
+                                num_edges, sigma, out, out_f64, err, s);
 }

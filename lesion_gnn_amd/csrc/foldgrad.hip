@@ -9,7 +9,7 @@
 // fp32 FMA chains (db_0's in double), every output element one thread's chain in index order (no
 // atomics, the same bits on every run). The open tiles' directly formed totals are added when
 // given.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -167,7 +167,5 @@ extern "C" int lgnn_gcn_fold_wgrad(const float* T, const float* g, const float* 
     if (w < 4 || w > FW || w % 4 != 0) return LGNN_EINVAL;
   FoldArgs a = {T, g, W0, b0, W1, dW0_open, db0_open, dW1_open, live, dW0, db0, dW1, d_in, w1, w2};
   const unsigned grid = (unsigned)((w1 + FR - 1) / FR + (w2 + FR - 1) / FR);
-  hipLaunchKernelGGL(k_fold_wgrad, dim3(grid), dim3(FT), 0, as_stream(stream), a);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_fold_wgrad, dim3(grid), dim3(FT), as_stream(stream), a);
 }

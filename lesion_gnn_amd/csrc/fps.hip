@@ -11,7 +11,7 @@
 // running minimum distances in registers (PER points per thread, point i on thread i % FT);
 // larger graphs keep d in the caller's workspace and re-read pos. Per pick: a wave reduction of
 // (d, index) and one cross-wave step through LDS (double-buffered: one barrier per pick).
-#include "common.h"
+#include "launch.h"
 #include "geom.h"
 
 namespace {
@@ -128,12 +128,8 @@ extern "C" int lgnn_fps(const double* pos, int64_t N, int dims, const int32_t* p
   if (B == 0 || num_out == 0) return LGNN_OK;
   hipStream_t s = as_stream(stream);
   double* dws = static_cast<double*>(workspace);
-  if (dims == 2)
-    hipLaunchKernelGGL(k_fps<2>, dim3((unsigned)B), dim3(FT), 0, s, pos, ptr, optr, start, idx,
-                       dws);
-  else
-    hipLaunchKernelGGL(k_fps<3>, dim3((unsigned)B), dim3(FT), 0, s, pos, ptr, optr, start, idx,
-                       dws);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<3, 2>(dims, [&](auto D) {
+    enqueue(k_fps<D>, dim3((unsigned)B), dim3(FT), s, pos, ptr, optr, start, idx, dws);
+  });
+  return last_error();
 }

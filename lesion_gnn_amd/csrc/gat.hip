@@ -12,7 +12,7 @@
 // adjacent lanes and per-head dot products are xor-butterflies inside the half wave. Rows are
 // visited in CSR order (= PyG's edge order; the self loop is last), so sums follow PyG's
 // scatter_add_ order.
-#include "common.h"
+#include "launch.h"
 #include "tile_util.h"
 
 namespace {
@@ -1522,30 +1522,16 @@ inline bool pipe2_ok(int H, int C) {
 
 // persistent grid of a row-pipelined kernel: the workgroups one launch keeps resident (occupancy
 // API, cached per device and kernel), LGNN_OPT_GAT_BPC per CU if set
-template <typename K>
-inline unsigned pipe_grid(K kernel, int slot, int64_t M) {
-  static int cap[16][24];  // [device][kernel slot]
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  dev &= 15;
-  if (cap[dev][slot] <= 0) {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-      cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, NT, 0) != hipSuccess || per < 1)
-      per = 4;
-    cap[dev][slot] = cus * per;
-  }
-  int64_t c = cap[dev][slot];
+template <auto K>
+inline dim3 pipe_grid(int64_t M) {
+  const int dev = current_device(), cus = device_cus(dev), per = workgroups_per_cu<K>(NT, dev);
+  int64_t c = (int64_t)(cus > 0 ? cus : 256) * (per > 0 ? per : 4);  // a failed query's stand-ins
   if (const int bpc = lgnn_option(LGNN_OPT_GAT_BPC)) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      c = (int64_t)cus * bpc;
+    if (cus > 0) c = (int64_t)cus * bpc;
   }
   int64_t g = (M + RB - 1) / RB;
   if (g > c) g = c;
-  return (unsigned)(g < 8 ? 8 : g);
+  return dim3((unsigned)(g < 8 ? 8 : g));
 }
 
 // C a power of two in [4, 512] (the reference sweep: widths 32..512, heads 1/2/4/8), H*C <= 512
@@ -1567,17 +1553,12 @@ extern "C" int lgnn_gat_att(const float* XP, int64_t M, int H, int C, const floa
   if (M < 0 || !shape_ok(H, C) || !att_src || !att_dst || (M > 0 && (!XP || !a_s || !a_d)))
     return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-#define LGNN_ATT(NS_)                                                                       \
-  hipLaunchKernelGGL(k_gat_att<NS_>, dim3(row_grid(M)), dim3(NT), 0, as_stream(stream), XP, M, H, \
-                     C, att_src, att_dst, a_s, a_d)
-  switch (ns_of(C)) {
-    case 1: LGNN_ATT(1); break;
-    case 2: LGNN_ATT(2); break;
-    default: LGNN_ATT(4); break;
-  }
-#undef LGNN_ATT
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_OK;
+  one_of<4, 1, 2>(ns_of(C), [&](auto NS) {
+    r = launch(k_gat_att<NS>, row_grid(M), dim3(NT), as_stream(stream), XP, M, H, C, att_src,
+               att_dst, a_s, a_d);
+  });
+  return r;
 }
 
 extern "C" int lgnn_gat_fwd(const int32_t* rowptr, const int32_t* col, const float* XP,
@@ -1589,52 +1570,25 @@ extern "C" int lgnn_gat_fwd(const int32_t* rowptr, const int32_t* col, const flo
   if (M > 0 && (!rowptr || !col || !XP || !a_s || !a_d || !Y)) return LGNN_EINVAL;
   if (!bytes_ok(M, H, C)) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-  if (pipe2_ok(H, C)) {
-#define LGNN_GFS(A_, SLOT_)                                                                     \
-  hipLaunchKernelGGL((k_gat_fwd_ps<A_, 2>), dim3(pipe_grid(k_gat_fwd_ps<A_, 2>, SLOT_, M)),        \
-                     dim3(NT), 0, as_stream(stream), rowptr, col, XP, a_s, a_d, M, H, C, s0,       \
-                     negative_slope, edge_mask, bias, alpha, Y, Y_bf16)
-    for (int s0 = 0; 128 * s0 < H * C; s0 += 2) {
-      if (act == LGNN_ACT_ELU) LGNN_GFS(LGNN_ACT_ELU, 6);
-      else LGNN_GFS(LGNN_ACT_NONE, 7);
-    }
-#undef LGNN_GFS
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
-  }
-  if (pipe_ok(H, C)) {
-#define LGNN_GFP(A_, HS_, SLOT_)                                                                \
-  hipLaunchKernelGGL((k_gat_fwd_p<A_, HS_>), dim3(pipe_grid(k_gat_fwd_p<A_, HS_>, SLOT_, M)),      \
-                     dim3(NT), 0, as_stream(stream), rowptr, col, XP, a_s, a_d, M, H, C,            \
-                     negative_slope, edge_mask, bias, alpha, Y, Y_bf16)
-    if (H <= 4) {
-      if (act == LGNN_ACT_ELU) LGNN_GFP(LGNN_ACT_ELU, 1, 0); else LGNN_GFP(LGNN_ACT_NONE, 1, 1);
+  const hipStream_t s = as_stream(stream);
+  one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+    if (pipe2_ok(H, C)) {
+      for (int s0 = 0; 128 * s0 < H * C; s0 += 2)
+        enqueue(k_gat_fwd_ps<A, 2>, pipe_grid<k_gat_fwd_ps<A, 2>>(M), dim3(NT), s, rowptr, col, XP,
+                a_s, a_d, M, H, C, s0, negative_slope, edge_mask, bias, alpha, Y, Y_bf16);
+    } else if (pipe_ok(H, C)) {
+      one_of<2, 1>(H <= 4 ? 1 : 2, [&](auto HS) {
+        enqueue(k_gat_fwd_p<A, HS>, pipe_grid<k_gat_fwd_p<A, HS>>(M), dim3(NT), s, rowptr, col, XP,
+                a_s, a_d, M, H, C, negative_slope, edge_mask, bias, alpha, Y, Y_bf16);
+      });
     } else {
-      if (act == LGNN_ACT_ELU) LGNN_GFP(LGNN_ACT_ELU, 2, 12); else LGNN_GFP(LGNN_ACT_NONE, 2, 13);
+      one_of<4, 1, 2>(ns_of(C), [&](auto NS) {
+        enqueue(k_gat_fwd<A, NS>, row_grid(M), dim3(NT), s, rowptr, col, XP, a_s, a_d, M, H, C,
+                negative_slope, edge_mask, bias, alpha, Y, Y_bf16);
+      });
     }
-#undef LGNN_GFP
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
-  }
-#define LGNN_GF(A_, NS_)                                                                     \
-  hipLaunchKernelGGL((k_gat_fwd<A_, NS_>), dim3(row_grid(M)), dim3(NT), 0, as_stream(stream),    \
-                     rowptr, col, XP, a_s, a_d, M, H, C, negative_slope, edge_mask, bias, alpha, Y, \
-                     Y_bf16)
-#define LGNN_GF_NS(A_)                    \
-  switch (ns_of(C)) {                     \
-    case 1: LGNN_GF(A_, 1); break;        \
-    case 2: LGNN_GF(A_, 2); break;        \
-    default: LGNN_GF(A_, 4); break;       \
-  }
-  if (act == LGNN_ACT_ELU) {
-    LGNN_GF_NS(LGNN_ACT_ELU)
-  } else {
-    LGNN_GF_NS(LGNN_ACT_NONE)
-  }
-#undef LGNN_GF_NS
-#undef LGNN_GF
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  });
+  return last_error();
 }
 
 namespace {
@@ -1652,72 +1606,28 @@ int gat_bwd_edge_launch(const int32_t* rowptr, const int32_t* col, const float* 
   if (!bytes_ok(M, H, C)) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
   const PoolGrad p = pg ? *pg : PoolGrad{};
-  if (pipe2_ok(H, C)) {
-#define LGNN_GBS(A_, POOL_, SLOT_)                                                             \
-  hipLaunchKernelGGL((k_gat_bwd_edge_ps<A_, POOL_, 2>),                                         \
-                     dim3(pipe_grid(k_gat_bwd_edge_ps<A_, POOL_, 2>, SLOT_, M)), dim3(NT), 0,    \
-                     as_stream(stream), rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, M, H, \
-                     C, s0, slope, dZ, da_e, da_d, p)
-    for (int s0 = 0; 128 * s0 < H * C; s0 += 2) {
-      if (act == LGNN_ACT_ELU) {
-        if (pg) LGNN_GBS(LGNN_ACT_ELU, true, 8); else LGNN_GBS(LGNN_ACT_ELU, false, 9);
-      } else {
-        if (pg) LGNN_GBS(LGNN_ACT_NONE, true, 10); else LGNN_GBS(LGNN_ACT_NONE, false, 11);
-      }
-    }
-#undef LGNN_GBS
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
-  }
-  if (pipe_ok(H, C)) {
-#define LGNN_GBP(A_, POOL_, HS_, SLOT_)                                                        \
-  hipLaunchKernelGGL((k_gat_bwd_edge_p<A_, POOL_, HS_>),                                        \
-                     dim3(pipe_grid(k_gat_bwd_edge_p<A_, POOL_, HS_>, SLOT_, M)), dim3(NT), 0,   \
-                     as_stream(stream), rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, M, H, \
-                     C, slope, dZ, da_e, da_d, p)
-    if (H <= 4) {
-      if (act == LGNN_ACT_ELU) {
-        if (pg) LGNN_GBP(LGNN_ACT_ELU, true, 1, 2); else LGNN_GBP(LGNN_ACT_ELU, false, 1, 3);
-      } else {
-        if (pg) LGNN_GBP(LGNN_ACT_NONE, true, 1, 4); else LGNN_GBP(LGNN_ACT_NONE, false, 1, 5);
-      }
+  const hipStream_t s = as_stream(stream);
+  const bool pool = pg != nullptr;
+  one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) { one_of<false, true>(pool, [&](auto POOL) {
+    if (pipe2_ok(H, C)) {
+      for (int s0 = 0; 128 * s0 < H * C; s0 += 2)
+        enqueue(k_gat_bwd_edge_ps<A, POOL, 2>, pipe_grid<k_gat_bwd_edge_ps<A, POOL, 2>>(M),
+                dim3(NT), s, rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, M, H, C, s0, slope,
+                dZ, da_e, da_d, p);
+    } else if (pipe_ok(H, C)) {
+      one_of<2, 1>(H <= 4 ? 1 : 2, [&](auto HS) {
+        enqueue(k_gat_bwd_edge_p<A, POOL, HS>, pipe_grid<k_gat_bwd_edge_p<A, POOL, HS>>(M),
+                dim3(NT), s, rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, M, H, C, slope, dZ,
+                da_e, da_d, p);
+      });
     } else {
-      if (act == LGNN_ACT_ELU) {
-        if (pg) LGNN_GBP(LGNN_ACT_ELU, true, 2, 14); else LGNN_GBP(LGNN_ACT_ELU, false, 2, 15);
-      } else {
-        if (pg) LGNN_GBP(LGNN_ACT_NONE, true, 2, 16); else LGNN_GBP(LGNN_ACT_NONE, false, 2, 17);
-      }
+      one_of<4, 1, 2>(ns_of(C), [&](auto NS) {
+        enqueue(k_gat_bwd_edge<A, NS, POOL>, row_grid(M), dim3(NT), s, rowptr, col, XP, a_s, a_d,
+                alpha, edge_mask, dY, Y, M, H, C, slope, dZ, da_e, da_d, p);
+      });
     }
-#undef LGNN_GBP
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
-  }
-#define LGNN_GB(A_, NS_)                                                                        \
-  do {                                                                                          \
-    if (pg)                                                                                     \
-      hipLaunchKernelGGL((k_gat_bwd_edge<A_, NS_, true>), dim3(row_grid(M)), dim3(NT), 0,        \
-                         as_stream(stream), rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, \
-                         M, H, C, slope, dZ, da_e, da_d, p);                                    \
-    else                                                                                        \
-      hipLaunchKernelGGL((k_gat_bwd_edge<A_, NS_, false>), dim3(row_grid(M)), dim3(NT), 0,       \
-                         as_stream(stream), rowptr, col, XP, a_s, a_d, alpha, edge_mask, dY, Y, \
-                         M, H, C, slope, dZ, da_e, da_d, p);                                    \
-  } while (0)
-#define LGNN_GB_NS(A_)                    \
-  switch (ns_of(C)) {                     \
-    case 1: LGNN_GB(A_, 1); break;        \
-    case 2: LGNN_GB(A_, 2); break;        \
-    default: LGNN_GB(A_, 4); break;       \
-  }
-  if (act == LGNN_ACT_ELU) {
-    LGNN_GB_NS(LGNN_ACT_ELU)
-  } else {
-    LGNN_GB_NS(LGNN_ACT_NONE)
-  }
-#undef LGNN_GB_NS
-#undef LGNN_GB
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  }); });
+  return last_error();
 }
 }  // namespace
 
@@ -1764,36 +1674,22 @@ extern "C" int lgnn_gat_bwd_node(const int32_t* tptr, const int32_t* tidx, const
   if (M > 0 && (!tptr || !tidx || !tmap || !alpha || !da_e || !da_d || !dZ || !XP || !dXP))
     return LGNN_EINVAL;
   if (!bytes_ok(M, H, C)) return LGNN_EINVAL;
+  const hipStream_t s = as_stream(stream);
+  const dim3 grid(num_partials), block(NT);
   if (pipe2_ok(H, C) && M > 0) {
     for (int s0 = 0; 128 * s0 < H * C; s0 += 2)
-      hipLaunchKernelGGL(k_gat_bwd_node_ps<2>, dim3(num_partials), dim3(NT), 0,
-                         as_stream(stream), tptr, tidx, tmap, alpha, edge_mask, da_e, da_d, dZ, XP,
-                         att_src, att_dst, M, H, C, s0, dXP, partials, dXP_bf16);
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
+      enqueue(k_gat_bwd_node_ps<2>, grid, block, s, tptr, tidx, tmap, alpha, edge_mask, da_e, da_d,
+              dZ, XP, att_src, att_dst, M, H, C, s0, dXP, partials, dXP_bf16);
+  } else if (pipe_ok(H, C) && M > 0) {
+    one_of<2, 1>(H <= 4 ? 1 : 2, [&](auto HS) {
+      enqueue(k_gat_bwd_node_p<HS>, grid, block, s, tptr, tidx, tmap, alpha, edge_mask, da_e, da_d,
+              dZ, XP, att_src, att_dst, M, H, C, dXP, partials, dXP_bf16);
+    });
+  } else {
+    one_of<4, 1, 2>((H * C + 127) / 128, [&](auto NST) {
+      enqueue(k_gat_bwd_node<NST>, grid, block, s, tptr, tidx, tmap, alpha, edge_mask, da_e, da_d,
+              dZ, XP, att_src, att_dst, M, H, C, dXP, partials, dXP_bf16);
+    });
   }
-  if (pipe_ok(H, C) && M > 0) {
-    if (H <= 4)
-      hipLaunchKernelGGL(k_gat_bwd_node_p<1>, dim3(num_partials), dim3(NT), 0, as_stream(stream),
-                         tptr, tidx, tmap, alpha, edge_mask, da_e, da_d, dZ, XP, att_src, att_dst,
-                         M, H, C, dXP, partials, dXP_bf16);
-    else
-      hipLaunchKernelGGL(k_gat_bwd_node_p<2>, dim3(num_partials), dim3(NT), 0, as_stream(stream),
-                         tptr, tidx, tmap, alpha, edge_mask, da_e, da_d, dZ, XP, att_src, att_dst,
-                         M, H, C, dXP, partials, dXP_bf16);
-    LGNN_LAUNCH_CHECK();
-    return LGNN_OK;
-  }
-#define LGNN_GN(NST_)                                                                        \
-  hipLaunchKernelGGL(k_gat_bwd_node<NST_>, dim3(num_partials), dim3(NT), 0, as_stream(stream),  \
-                     tptr, tidx, tmap, alpha, edge_mask, da_e, da_d, dZ, XP, att_src, att_dst, M, \
-                     H, C, dXP, partials, dXP_bf16)
-  switch ((H * C + 127) / 128) {
-    case 1: LGNN_GN(1); break;
-    case 2: LGNN_GN(2); break;
-    default: LGNN_GN(4); break;
-  }
-#undef LGNN_GN
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }

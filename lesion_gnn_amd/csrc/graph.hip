@@ -15,7 +15,7 @@
 //             order PyG's scatter_add_ visits a target's messages in), compute GCN weights,
 //             write back. Run for both CSRs.
 // The result is identical run to run.
-#include "common.h"
+#include "launch.h"
 #include "tile_util.h"
 #include "s3_util.h"
 
@@ -1201,7 +1201,7 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
       hipLaunchKernelGGL(k_prep, dim3(g + pblocks), dim3(kThreads), 0, s, ws.err, nzero,
                          tile_open, ntiles, batch, N, num_graphs, gptr, pj, g);
     }
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
   }
   if (N == 0) {
     if (hipMemsetAsync(rowptr, 0, 4, s) != hipSuccess) return (int)hipGetLastError();
@@ -1222,17 +1222,16 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
                          dim3(kThreads), 0, s, edge_index, E, N, loops, ws.cnt,
                          tptr ? ws.tcnt : nullptr, ws.err, lazy ? tile_open : nullptr, sa.verdict,
                          sa.nverdict);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     sa.summary_ready = sa.verdict != nullptr;
   }
   {
     const int64_t nblk = (N + 1 + kScanBlk - 1) / kScanBlk;
     const int64_t nsb = try_sorted ? (N + kSortedRows - 1) / kSortedRows : 0;
     dim3 sg((unsigned)(nsb > nblk ? nsb : nblk), tptr ? 2u : 1u);
-    hipLaunchKernelGGL(k_scan, sg, dim3(kScanT), 0, s, ws.cnt, ws.tcnt, N, add_loop, ws.stat,
-                       rowptr, tptr, ws.fill, ws.tfill, ws.dis, lazy ? tile_open : nullptr, sa,
-                       col, w, err_count, (int)nblk);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_scan, sg, dim3(kScanT), s, ws.cnt, ws.tcnt, N, add_loop, ws.stat,
+                             rowptr, tptr, ws.fill, ws.tfill, ws.dis, lazy ? tile_open : nullptr,
+                             sa, col, w, err_count, (int)nblk)) return e;
   }
   if (E > 0 && !skip_general) {
     if (small_edges(E))
@@ -1247,23 +1246,22 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
                          ws.eid, tptr, ws.tfill, tidx, ws.teid,
                          lazy ? tile_open + (N + 63) / 64 : nullptr,
                          try_sorted ? ws.verdict + kVerdictMax : nullptr);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
   }
   const int64_t nfin = (N + kFinR - 1) / kFinR;
   const int64_t fgx = (nfin + kFinWaves - 1) / kFinWaves;
   dim3 fg((unsigned)(fgx < kFinGrid ? fgx : kFinGrid), tptr ? 2u : 1u);
   // with tmap, the target side of k_finish also writes inv (edge id -> target-CSR position)
   if (!skip_general) {
-    hipLaunchKernelGGL(k_finish, fg, dim3(kThreads), 0, s, N, E, add_loop, norm, rowptr, col,
-                       ws.eid, w, tptr, tidx, ws.teid, tw, ws.dis, ws.err, err_count, tile_open,
-                       lazy, tmap ? ws.inv : nullptr,
-                       try_sorted ? ws.verdict + kVerdictMax : nullptr);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_finish, fg, dim3(kThreads), s, N, E, add_loop, norm, rowptr, col,
+                             ws.eid, w, tptr, tidx, ws.teid, tw, ws.dis, ws.err, err_count,
+                             tile_open, lazy, tmap ? ws.inv : nullptr,
+                             try_sorted ? ws.verdict + kVerdictMax : nullptr)) return e;
   }
   if (tmap) {
     const int g = grid_for(E + N, 2048);
-    hipLaunchKernelGGL(k_tmap, dim3(g), dim3(kThreads), 0, s, tptr, N, ws.teid, ws.inv, tmap);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_tmap, dim3(g), dim3(kThreads), s, tptr, N, ws.teid, ws.inv,
+                             tmap)) return e;
   }
   return LGNN_OK;
 }
@@ -1271,8 +1269,6 @@ static int graph_build(const int64_t* edge_index, int64_t E, int64_t N, int loop
 extern "C" int lgnn_batch_ptr(const int64_t* batch, int64_t M, int64_t B, int32_t* ptr,
                               void* stream) {
   if (M < 0 || B < 0 || !ptr || (M > 0 && !batch) || M > INT32_MAX) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_batch_ptr, dim3(grid_for(M + 1)), dim3(kThreads), 0, as_stream(stream),
-                     batch, M, B, ptr);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_batch_ptr, dim3(grid_for(M + 1)), dim3(kThreads), as_stream(stream), batch, M, B,
+                ptr);
 }

@@ -15,7 +15,7 @@
 // the candidates of its graphs form one contiguous node range, staged through LDS in chunks.
 // Each thread keeps its best KMAX (k rounded up to a power of two) in registers as a sorted
 // list; candidates arrive in index order, so strict comparisons keep ties in index order.
-#include "common.h"
+#include "launch.h"
 #include "geom.h"
 #include "wg.h"
 
@@ -115,22 +115,6 @@ __global__ __launch_bounds__(QT) void k_knn(const double* __restrict__ pos, int6
   }
 }
 
-template <int D>
-hipError_t launch_knn(int kmax, dim3 grid, hipStream_t s, const double* pos, int64_t N,
-                      const int64_t* batch, const int32_t* ptr, int k, int loop,
-                      const int64_t* eoff, int64_t E, int64_t* ei) {
-#define LGNN_KNN(KM) \
-  hipLaunchKernelGGL((k_knn<KM, D>), grid, dim3(QT), 0, s, pos, N, batch, ptr, k, loop, eoff, E, ei)
-  switch (kmax) {
-    case 4: LGNN_KNN(4); break;
-    case 8: LGNN_KNN(8); break;
-    case 16: LGNN_KNN(16); break;
-    default: LGNN_KNN(32); break;
-  }
-#undef LGNN_KNN
-  return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" size_t lgnn_knn_workspace_bytes(int64_t num_graphs) {
@@ -148,15 +132,14 @@ extern "C" int lgnn_knn_graph(const double* pos, int64_t N, int dims, const int6
   if (N == 0 || B == 0) return LGNN_OK;
   hipStream_t s = as_stream(stream);
   int64_t* eoff = static_cast<int64_t*>(workspace);
-  hipLaunchKernelGGL(k_knn_offsets, dim3(1), dim3(kScanTile), 0, s, ptr, B, k, loop, eoff);
-  LGNN_LAUNCH_CHECK();
+  int r = launch(k_knn_offsets, dim3(1), dim3(kScanTile), s, ptr, B, k, loop, eoff);
+  if (r != LGNN_OK) return r;
   const int kmax = k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32;  // the self loop is skipped, not
                                                                    // kept, when !loop
   const dim3 grid((unsigned)((N + QT - 1) / QT));
-  const hipError_t e =
-      dims == 2 ? launch_knn<2>(kmax, grid, s, pos, N, batch, ptr, k, loop, eoff, num_edges,
-                                edge_index)
-                : launch_knn<3>(kmax, grid, s, pos, N, batch, ptr, k, loop, eoff, num_edges,
-                                edge_index);
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  one_of<3, 2>(dims, [&](auto D) { one_of<32, 4, 8, 16>(kmax, [&](auto KM) {
+    r = launch(k_knn<KM, D>, grid, dim3(QT), s, pos, N, batch, ptr, k, loop, eoff, num_edges,
+               edge_index);
+  }); });
+  return r;
 }

@@ -6,7 +6,7 @@
 //   dz_i = g * w[y_i] / sum_j w[y_j] * (softmax(z_i) - onehot(y_i))
 // One workgroup; rows are summed in fixed order (per-thread strided partials, then a fixed
 // tree), so the loss is bitwise reproducible.
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace {
@@ -278,10 +278,8 @@ extern "C" int lgnn_ce_fwd(const float* logits, const int64_t* target, const flo
                            void* stream) {
   if (B <= 0 || C <= 0 || !logits || !target || !lse || !loss || !wsum || !bad)
     return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_ce_fwd<false>, dim3(1), dim3(CT), 0, as_stream(stream), logits, target,
-                     weight, B, C, lse, loss, wsum, bad, nullptr, nullptr);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_ce_fwd<false>, dim3(1), dim3(CT), as_stream(stream), logits, target, weight, B, C,
+                lse, loss, wsum, bad, nullptr, nullptr);
 }
 
 extern "C" int lgnn_ce_fwd_factors(const float* logits, const int64_t* target,
@@ -289,10 +287,8 @@ extern "C" int lgnn_ce_fwd_factors(const float* logits, const int64_t* target,
                                    float* wsum, int* bad, float* pm, float* wt, void* stream) {
   if (B <= 0 || C <= 0 || !logits || !target || !lse || !loss || !wsum || !bad || !pm || !wt)
     return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_ce_fwd<true>, dim3(1), dim3(CT), 0, as_stream(stream), logits, target,
-                     weight, B, C, lse, loss, wsum, bad, pm, wt);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_ce_fwd<true>, dim3(1), dim3(CT), as_stream(stream), logits, target, weight, B, C,
+                lse, loss, wsum, bad, pm, wt);
 }
 
 extern "C" int lgnn_ce_bwd(const float* logits, const int64_t* target, const float* weight,
@@ -300,11 +296,8 @@ extern "C" int lgnn_ce_bwd(const float* logits, const int64_t* target, const flo
                            const float* grad_loss, float* dlogits, void* stream) {
   if (B <= 0 || C <= 0 || !logits || !target || !lse || !wsum || !grad_loss || !dlogits)
     return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_ce_bwd, dim3((unsigned)((B * C + 255) / 256)), dim3(256), 0,
-                     as_stream(stream), logits, target, weight, B, C, lse, wsum, grad_loss,
-                     dlogits);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_ce_bwd, dim3((unsigned)((B * C + 255) / 256)), dim3(256), as_stream(stream),
+                logits, target, weight, B, C, lse, wsum, grad_loss, dlogits);
 }
 
 extern "C" int lgnn_regression_fwd(const float* z, const void* target, int target_is_i64,
@@ -317,8 +310,7 @@ extern "C" int lgnn_regression_fwd(const float* z, const void* target, int targe
   else
     hipLaunchKernelGGL(k_reg_fwd<float>, dim3(1), dim3(CT), 0, as_stream(stream), z,
                        static_cast<const float*>(target), B, lo, hi, smooth_l1, pred, loss);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_regression_bwd(const float* z, const void* target, int target_is_i64,
@@ -335,8 +327,7 @@ extern "C" int lgnn_regression_bwd(const float* z, const void* target, int targe
     hipLaunchKernelGGL(k_reg_bwd<float>, grid, dim3(256), 0, as_stream(stream), z,
                        static_cast<const float*>(target), B, lo, hi, smooth_l1, grad_loss,
                        grad_pred, dz);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_reduce_partials_multi(int n, const float* const* partials,
@@ -380,10 +371,8 @@ static int reduce_jobs(int n, const float* const* partials, const float* const* 
     if (len[j] > maxlen) maxlen = len[j];
   }
   if (maxlen == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_reduce_multi, dim3((unsigned)((maxlen + 63) / 64), (unsigned)n), dim3(RT),
-                     0, as_stream(stream), jobs);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_reduce_multi, dim3((unsigned)((maxlen + 63) / 64), (unsigned)n), dim3(RT),
+                as_stream(stream), jobs);
 }
 
 extern "C" int lgnn_reduce_jobs(int n, const float* const* partials, const float* const* factor,

@@ -12,7 +12,7 @@
 //                  counts added per sample with integer atomics (order-independent).
 //   k_eval_final   one workgroup: sums the per-sample counts in a fixed order, then thread 0 forms
 //                  every metric in double.
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace {
@@ -312,8 +312,7 @@ extern "C" int lgnn_eval_update(const float* z, const int64_t* target, const flo
     hipLaunchKernelGGL(k_eval_update<false>, dim3(1), dim3(CT), 0, as_stream(stream), z, target,
                        weight, B, C, 0, counts, loss_acc, scores, positive, capacity);
   }
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" size_t lgnn_eval_workspace_bytes(int64_t capacity) {
@@ -338,14 +337,12 @@ extern "C" int lgnn_eval_compute(const int64_t* counts, const double* loss_acc,
     hipError_t e = hipMemsetAsync(ws, 0, lgnn_eval_workspace_bytes(capacity), as_stream(stream));
     if (e != hipSuccess) return (int)e;
     const dim3 grid((unsigned)((capacity + RB - 1) / RB), LGNN_EVAL_RANK_SPLIT);
-    hipLaunchKernelGGL(k_eval_rank, grid, dim3(RB), 0, as_stream(stream),
-                       counts + C * C + LGNN_EVAL_NSEEN, scores, positive, capacity, ws);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_eval_rank, grid, dim3(RB), as_stream(stream),
+                             counts + C * C + LGNN_EVAL_NSEEN, scores, positive, capacity,
+                             ws)) return e;
   }
-  hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(CT), 0, as_stream(stream), counts, loss_acc,
-                     capacity, C, regression, ws, result);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_eval_final, dim3(1), dim3(CT), as_stream(stream), counts, loss_acc, capacity, C,
+                regression, ws, result);
 }
 
 extern "C" int lgnn_eval_merge(int C, int64_t* counts, double* loss_acc, float* scores,
@@ -358,9 +355,6 @@ extern "C" int lgnn_eval_merge(int C, int64_t* counts, double* loss_acc, float* 
   const bool stored = scores || positive || src_scores || src_positive;
   if (stored && (!scores || !positive || !src_scores || !src_positive || capacity < 0))
     return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_eval_merge, dim3(1), dim3(CT), 0, as_stream(stream), C, counts, loss_acc,
-                     scores, positive, src_counts, src_loss_acc, src_scores, src_positive,
-                     capacity);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_eval_merge, dim3(1), dim3(CT), as_stream(stream), C, counts, loss_acc, scores,
+                positive, src_counts, src_loss_acc, src_scores, src_positive, capacity);
 }

@@ -17,7 +17,7 @@
 //
 // Replaces (reference): nn.Linear in_proj/out_proj (gin.py:21,25), GCNConv/GINConv propagate +
 // lin (gin.py:23), F.elu (gin.py:31) and their autograd backward.
-#include "common.h"
+#include "launch.h"
 #include "tile.h"
 
 namespace {
@@ -506,17 +506,6 @@ __global__ __launch_bounds__(NT) void k_linear_dx(
   }
 }
 
-template <int GMODE, int ACT>
-hipError_t launch_dx(hipStream_t s, const float* dY, const int64_t* batch, const int32_t* gptr,
-                     int pool_mean, const int32_t* tptr, const int32_t* tidx, const float* tw,
-                     float tself, const float* H, int64_t M, int K, const float* W, int N,
-                     float* dXpre) {
-  dim3 grid((unsigned)((M + TM - 1) / TM), (unsigned)((K + KC - 1) / KC));
-  hipLaunchKernelGGL((k_linear_dx<GMODE, ACT>), grid, dim3(NT), 0, s, dY, batch, gptr, pool_mean,
-                     tptr, tidx, tw, tself, H, M, K, W, N, dXpre);
-  return hipGetLastError();
-}
-
 // out[i] = sum_p partial[p*len + i]: block = 16 waves x 64 columns; wave w sums p = w, w+16, ...
 // (all of its loads in flight), then the 16 wave sums are combined in fixed order.
 constexpr int RT = 1024;
@@ -623,38 +612,6 @@ int grid_partials(int64_t M, int N, int K) {
   return (int)(p < 1 ? 1 : p);
 }
 
-template <int GMODE, int ACT, bool GATHER, bool DX>
-hipError_t launch_bwd(dim3 grid, hipStream_t s, const float* dY, const int64_t* batch,
-                      const int32_t* gptr, int pool_mean, const int32_t* tptr,
-                      const int32_t* tidx, const float* tw, float tself, const float* H,
-                      const float* X, int64_t M, int K, const int32_t* rowptr, const int32_t* col,
-                      const float* w, float self_scale, const float* W, int N, float* dXpre,
-                      float* dWp, float* dbp) {
-  hipLaunchKernelGGL((k_linear_bwd<GMODE, ACT, GATHER, DX>), grid, dim3(NT), 0, s, dY, batch, gptr,
-                     pool_mean, tptr, tidx, tw, tself, H, X, M, K, rowptr, col, w, self_scale, W,
-                     N, dXpre, dWp, dbp);
-  return hipGetLastError();
-}
-
-template <int GMODE, int ACT>
-hipError_t dispatch_bwd2(bool gather, bool dx, dim3 grid, hipStream_t s, const float* dY,
-                         const int64_t* batch, const int32_t* gptr, int pool_mean,
-                         const int32_t* tptr, const int32_t* tidx, const float* tw, float tself,
-                         const float* H, const float* X, int64_t M, int K, const int32_t* rowptr,
-                         const int32_t* col, const float* w, float self_scale, const float* W,
-                         int N, float* dXpre, float* dWp, float* dbp) {
-#define LGNN_BWD_ARGS                                                                          \
-  grid, s, dY, batch, gptr, pool_mean, tptr, tidx, tw, tself, H, X, M, K, rowptr, col, w,      \
-      self_scale, W, N, dXpre, dWp, dbp
-  if (gather) {
-    if (dx) return launch_bwd<GMODE, ACT, true, true>(LGNN_BWD_ARGS);
-    return launch_bwd<GMODE, ACT, true, false>(LGNN_BWD_ARGS);
-  }
-  if (dx) return launch_bwd<GMODE, ACT, false, true>(LGNN_BWD_ARGS);
-  return launch_bwd<GMODE, ACT, false, false>(LGNN_BWD_ARGS);
-#undef LGNN_BWD_ARGS
-}
-
 }  // namespace
 
 extern "C" int lgnn_node_linear_fwd(const float* X, int64_t M, int K, const int32_t* rowptr,
@@ -679,35 +636,24 @@ extern "C" int lgnn_node_linear_fwd_tiles(const float* X, int64_t M, int K,
   const int64_t gx = (M + TM - 1) / TM;
   if (gx > INT32_MAX) return LGNN_EINVAL;
   hipStream_t s = as_stream(stream);
-  if (lgnn_tile_fits(M, K, N)) {
-    const hipError_t e = lgnn_tile_fwd(s, X, M, K, rowptr, col, w, self_scale, W, b, N, act, Y,
-                                       gather ? S_out : nullptr, tile_open, want_open);
-    return e == hipSuccess ? LGNN_OK : (int)e;
-  }
+  if (lgnn_tile_fits(M, K, N))
+    return lgnn_tile_fwd(s, X, M, K, rowptr, col, w, self_scale, W, b, N, act, Y,
+                         gather ? S_out : nullptr, tile_open, want_open);
   if (tile_open) return LGNN_EINVAL;  // tile selection only on the fast path
   if (S_out) return LGNN_EINVAL;  // S_out only on the fast path (K, N <= 128)
   dim3 grid((unsigned)gx, (unsigned)((N + TN - 1) / TN));
   const bool vec = (K & 3) == 0;
-#define LGNN_FWD(G, V, A)                                                                         \
-  hipLaunchKernelGGL((k_linear_fwd<G, V, A>), grid, dim3(NT), 0, s, X, M, K, rowptr, col, w,      \
-                     self_scale, W, b, N, Y)
-  if (gather) {
-    if (act == LGNN_ACT_ELU) LGNN_FWD(true, true, LGNN_ACT_ELU);
-    else LGNN_FWD(true, true, LGNN_ACT_NONE);
-  } else if (vec) {
-    if (act == LGNN_ACT_ELU) LGNN_FWD(false, true, LGNN_ACT_ELU);
-    else LGNN_FWD(false, true, LGNN_ACT_NONE);
-  } else {
-    if (act == LGNN_ACT_ELU) LGNN_FWD(false, false, LGNN_ACT_ELU);
-    else LGNN_FWD(false, false, LGNN_ACT_NONE);
-  }
-#undef LGNN_FWD
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_EINVAL;
+  one_of<false, true>(gather, [&](auto G) { one_of<false, true>(vec, [&](auto V) {
+    one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+      if constexpr (V || !G)  // a gathered K is a multiple of 4 (checked above)
+        r = launch(k_linear_fwd<G, V, A>, grid, dim3(NT), s, X, M, K, rowptr, col, w, self_scale,
+                   W, b, N, Y);
+    }); }); });
+  return r;
 }
 
 // The fast path applies when the prologue is direct (S streamed, not re-gathered).
-static hipStream_t s_(void* p) { return as_stream(p); }
 static bool bwd_fast(int64_t M, int N, int K, bool gather) {
   return !gather && lgnn_tile_fits(M, K, N);
 }
@@ -756,58 +702,40 @@ extern "C" int lgnn_node_linear_bwd_tiles(int grad_mode, const float* dY, const 
   if (grad_mode < 0 || grad_mode > 2 || (M > 0 && (!dY || !X))) return LGNN_EINVAL;
   const bool gather = rowptr != nullptr;
   if (gather && (!col || (K & 3))) return LGNN_EINVAL;
-  if (fast && M > 0) {
-    const hipError_t ef = lgnn_tile_bwd(s_(stream), grad_mode, dY, batch, gptr, pool_mean, tptr,
-                                        tidx, tw, tself, H, act, X, M, K, W, N, dXpre, dW_partial,
-                                        db_partial, num_partials, tile_open, want_open,
-                                        accumulate);
-    return ef == hipSuccess ? LGNN_OK : (int)ef;
-  }
+  hipStream_t s = as_stream(stream);
+  if (fast && M > 0)
+    return lgnn_tile_bwd(s, grad_mode, dY, batch, gptr, pool_mean, tptr, tidx, tw, tself, H, act,
+                         X, M, K, W, N, dXpre, dW_partial, db_partial, num_partials, tile_open,
+                         want_open, accumulate);
   const bool dx_sep = dXpre != nullptr && N > TN;  // dZ W needs every output block: own kernel
   const bool dx = dXpre != nullptr && !dx_sep;
-  hipStream_t s = as_stream(stream);
-  if (dx_sep && M > 0) {
-    hipError_t e2;
-#define LGNN_DX_CALL(GM, AC) \
-  launch_dx<GM, AC>(s, dY, batch, gptr, pool_mean, tptr, tidx, tw, tself, H, M, K, W, N, dXpre)
-    if (act == LGNN_ACT_ELU) {
-      if (grad_mode == LGNN_GRAD_DIRECT) e2 = LGNN_DX_CALL(LGNN_GRAD_DIRECT, LGNN_ACT_ELU);
-      else if (grad_mode == LGNN_GRAD_POOL) e2 = LGNN_DX_CALL(LGNN_GRAD_POOL, LGNN_ACT_ELU);
-      else e2 = LGNN_DX_CALL(LGNN_GRAD_TRANSPOSE, LGNN_ACT_ELU);
-    } else {
-      if (grad_mode == LGNN_GRAD_DIRECT) e2 = LGNN_DX_CALL(LGNN_GRAD_DIRECT, LGNN_ACT_NONE);
-      else if (grad_mode == LGNN_GRAD_POOL) e2 = LGNN_DX_CALL(LGNN_GRAD_POOL, LGNN_ACT_NONE);
-      else e2 = LGNN_DX_CALL(LGNN_GRAD_TRANSPOSE, LGNN_ACT_NONE);
-    }
-#undef LGNN_DX_CALL
-    if (e2 != hipSuccess) return (int)e2;
-  }
-  dim3 grid((unsigned)num_partials, (unsigned)((N + TN - 1) / TN), (unsigned)((K + KC - 1) / KC));
-  hipError_t e;
-#define LGNN_BWD_CALL(GM, AC)                                                                    \
-  dispatch_bwd2<GM, AC>(gather, dx, grid, s, dY, batch, gptr, pool_mean, tptr, tidx, tw, tself, H, \
-                        X, M, K, rowptr, col, w, self_scale, W, N, dXpre, dW_partial, db_partial)
-  if (act == LGNN_ACT_ELU) {
-    if (grad_mode == LGNN_GRAD_DIRECT) e = LGNN_BWD_CALL(LGNN_GRAD_DIRECT, LGNN_ACT_ELU);
-    else if (grad_mode == LGNN_GRAD_POOL) e = LGNN_BWD_CALL(LGNN_GRAD_POOL, LGNN_ACT_ELU);
-    else e = LGNN_BWD_CALL(LGNN_GRAD_TRANSPOSE, LGNN_ACT_ELU);
-  } else {
-    if (grad_mode == LGNN_GRAD_DIRECT) e = LGNN_BWD_CALL(LGNN_GRAD_DIRECT, LGNN_ACT_NONE);
-    else if (grad_mode == LGNN_GRAD_POOL) e = LGNN_BWD_CALL(LGNN_GRAD_POOL, LGNN_ACT_NONE);
-    else e = LGNN_BWD_CALL(LGNN_GRAD_TRANSPOSE, LGNN_ACT_NONE);
-  }
-#undef LGNN_BWD_CALL
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  const dim3 grid_dx((unsigned)((M + TM - 1) / TM), (unsigned)((K + KC - 1) / KC));
+  const dim3 grid((unsigned)num_partials, (unsigned)((N + TN - 1) / TN),
+                  (unsigned)((K + KC - 1) / KC));
+  int r = LGNN_OK;
+  one_of<LGNN_GRAD_TRANSPOSE, LGNN_GRAD_DIRECT, LGNN_GRAD_POOL>(grad_mode, [&](auto GM) {
+    one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+      if (dx_sep && M > 0) {  // its error is read before the dW launch
+        r = launch(k_linear_dx<GM, A>, grid_dx, dim3(NT), s, dY, batch, gptr, pool_mean, tptr,
+                   tidx, tw, tself, H, M, K, W, N, dXpre);
+        if (r != LGNN_OK) return;
+      }
+      one_of<false, true>(gather, [&](auto G) { one_of<false, true>(dx, [&](auto DX) {
+        r = launch(k_linear_bwd<GM, A, G, DX>, grid, dim3(NT), s, dY, batch, gptr, pool_mean, tptr,
+                   tidx, tw, tself, H, X, M, K, rowptr, col, w, self_scale, W, N, dXpre,
+                   dW_partial, db_partial);
+      }); });
+    });
+  });
+  return r;
 }
 
 extern "C" int lgnn_reduce_partials(const float* partial, int P, int64_t len, float* out,
                                     void* stream) {
   if (P <= 0 || len < 0 || !partial || !out) return LGNN_EINVAL;
   if (len == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_reduce, dim3((unsigned)((len + 63) / 64)), dim3(RT), 0, as_stream(stream),
-                     partial, P, len, out);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_reduce, dim3((unsigned)((len + 63) / 64)), dim3(RT), as_stream(stream), partial,
+                P, len, out);
 }
 
 extern "C" int lgnn_spmm(const int32_t* rowptr, const int32_t* col, const float* w,
@@ -815,9 +743,7 @@ extern "C" int lgnn_spmm(const int32_t* rowptr, const int32_t* col, const float*
                          void* stream) {
   if (M < 0 || D <= 0 || (D & 3) || !rowptr || !col || (M > 0 && (!X || !Y))) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_spmm_tile,
-                     dim3((unsigned)((M + TM - 1) / TM), (unsigned)((D + kSpC - 1) / kSpC)),
-                     dim3(NT), 0, as_stream(stream), rowptr, col, w, self_scale, X, M, D, Y);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_spmm_tile,
+                dim3((unsigned)((M + TM - 1) / TM), (unsigned)((D + kSpC - 1) / kSpC)), dim3(NT),
+                as_stream(stream), rowptr, col, w, self_scale, X, M, D, Y);
 }

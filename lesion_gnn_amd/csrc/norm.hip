@@ -11,7 +11,7 @@
 // consecutive columns each (blockIdx.y = 128-column chunk); the block's 8 half-wave row groups
 // stride rows, so per-column constants stay in registers and every row access is one 16-B load
 // per lane (512 contiguous bytes per half-wave). Sums: four rows in flight per thread.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -344,13 +344,11 @@ extern "C" int lgnn_bn_stats(const float* Z, int64_t M, int N, double* sums, voi
   hipStream_t s = as_stream(stream);
   const int P = row_blocks(M);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL((k_colsum<0, LGNN_ACT_ELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
-                     nullptr, nullptr, M, N, nullptr, nullptr, nullptr, nullptr, part);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)),
-                     dim3(NT), 0, s, part, P, 2 * N, sums);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  if (const int e = launch(k_colsum<0, LGNN_ACT_ELU>, dim3(P, (N + 127) / 128), dim3(NT), s, Z,
+                           nullptr, nullptr, M, N, nullptr, nullptr, nullptr, nullptr,
+                           part)) return e;
+  return launch(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)), dim3(NT), s,
+                part, P, 2 * N, sums);
 }
 
 extern "C" int lgnn_bn_finalize(const double* sums, double count, const float* gamma,
@@ -362,11 +360,9 @@ extern "C" int lgnn_bn_finalize(const double* sums, double count, const float* g
   if (training && (!sums || count <= 0.0)) return LGNN_EINVAL;
   if (!training && (!running_mean || !running_var)) return LGNN_EINVAL;
   if ((running_mean == nullptr) != (running_var == nullptr)) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_bn_finalize, dim3((N + NT - 1) / NT), dim3(NT), 0, as_stream(stream), sums,
-                     count, gamma, beta, eps, momentum, training, N, running_mean, running_var,
-                     num_batches_tracked, mean, invstd, scale, shift);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_bn_finalize, dim3((N + NT - 1) / NT), dim3(NT), as_stream(stream), sums, count,
+                gamma, beta, eps, momentum, training, N, running_mean, running_var,
+                num_batches_tracked, mean, invstd, scale, shift);
 }
 
 extern "C" int lgnn_bn_act_a(const float* Z, int64_t M, int N, const float* scale,
@@ -376,14 +372,11 @@ extern "C" int lgnn_bn_act_a(const float* Z, int64_t M, int N, const float* scal
     return LGNN_EINVAL;
   if (act != LGNN_ACT_ELU && act != LGNN_ACT_RELU) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-  if (act == LGNN_ACT_ELU)
-    hipLaunchKernelGGL(k_bn_act<LGNN_ACT_ELU>, ew_grid(M, N), dim3(NT), 0, as_stream(stream), Z,
-                       M, N, scale, shift, mask, A);
-  else
-    hipLaunchKernelGGL(k_bn_act<LGNN_ACT_RELU>, ew_grid(M, N), dim3(NT), 0, as_stream(stream), Z,
-                       M, N, scale, shift, mask, A);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<LGNN_ACT_RELU, LGNN_ACT_ELU>(act, [&](auto ACT) {
+    enqueue(k_bn_act<ACT>, ew_grid(M, N), dim3(NT), as_stream(stream), Z, M, N, scale, shift, mask,
+            A);
+  });
+  return last_error();
 }
 
 extern "C" int lgnn_bn_act(const float* Z, int64_t M, int N, const float* scale,
@@ -403,17 +396,13 @@ extern "C" int lgnn_bn_bwd_stats_a(const float* dA, const float* Z, const float*
   hipStream_t s = as_stream(stream);
   const int P = row_blocks(M);
   double* part = static_cast<double*>(workspace);
-  if (act == LGNN_ACT_ELU)
-    hipLaunchKernelGGL((k_colsum<1, LGNN_ACT_ELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
-                       dA, mask, M, N, scale, shift, mean, invstd, part);
-  else
-    hipLaunchKernelGGL((k_colsum<1, LGNN_ACT_RELU>), dim3(P, (N + 127) / 128), dim3(NT), 0, s, Z,
-                       dA, mask, M, N, scale, shift, mean, invstd, part);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)),
-                     dim3(NT), 0, s, part, P, 2 * N, sums);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<LGNN_ACT_RELU, LGNN_ACT_ELU>(act, [&](auto ACT) {
+    enqueue(k_colsum<1, ACT>, dim3(P, (N + 127) / 128), dim3(NT), s, Z, dA, mask, M, N, scale,
+            shift, mean, invstd, part);
+  });
+  if (const int e = last_error()) return e;
+  return launch(k_colsum_reduce, dim3((2 * N + NT / RED_SPLIT - 1) / (NT / RED_SPLIT)), dim3(NT), s,
+                part, P, 2 * N, sums);
 }
 
 extern "C" int lgnn_bn_bwd_stats(const float* dA, const float* Z, const float* mask, int64_t M,
@@ -436,8 +425,7 @@ extern "C" int lgnn_bn_partials_reduce(const double* part, int num_partials, int
     hipLaunchKernelGGL((k_bn_reduce_tail<false, false>), grid, dim3(NT), 0, as_stream(stream),
                        part, num_partials, N, sums, 0.0, nullptr, nullptr, 0.f, 0.f, 0, nullptr,
                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_bn_partials_finalize(const double* part, int num_partials, int N,
@@ -450,12 +438,10 @@ extern "C" int lgnn_bn_partials_finalize(const double* part, int num_partials, i
   if (num_partials <= 0 || N <= 0 || !part || !sums || count <= 0.0) return LGNN_EINVAL;
   if (!mean || !invstd || !scale || !shift) return LGNN_EINVAL;
   if ((running_mean == nullptr) != (running_var == nullptr)) return LGNN_EINVAL;
-  hipLaunchKernelGGL((k_bn_reduce_tail<true, false>), dim3((unsigned)((N + 7) / 8)), dim3(NT),
-                     0, as_stream(stream), part, num_partials, N, sums, count, gamma, beta, eps,
-                     momentum, 1, running_mean, running_var, num_batches_tracked, mean, invstd,
-                     scale, shift, nullptr, nullptr);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_bn_reduce_tail<true, false>, dim3((unsigned)((N + 7) / 8)), dim3(NT),
+                as_stream(stream), part, num_partials, N, sums, count, gamma, beta, eps, momentum,
+                1, running_mean, running_var, num_batches_tracked, mean, invstd, scale, shift,
+                nullptr, nullptr);
 }
 
 extern "C" int lgnn_bn_bwd_apply_a(const float* dA, const float* Z, const float* mask,
@@ -470,18 +456,15 @@ extern "C" int lgnn_bn_bwd_apply_a(const float* dA, const float* Z, const float*
   hipStream_t s = as_stream(stream);
   if (M > 0) {
     if (!dA || !Z || !dZ) return LGNN_EINVAL;
-    if (act == LGNN_ACT_ELU)
-      hipLaunchKernelGGL(k_bn_bwd_apply<LGNN_ACT_ELU>, ew_grid(M, N), dim3(NT), 0, s, dA, Z, mask,
-                         M, N, scale, shift, mean, invstd, sums, count, training, dZ);
-    else
-      hipLaunchKernelGGL(k_bn_bwd_apply<LGNN_ACT_RELU>, ew_grid(M, N), dim3(NT), 0, s, dA, Z,
-                         mask, M, N, scale, shift, mean, invstd, sums, count, training, dZ);
-    LGNN_LAUNCH_CHECK();
+    one_of<LGNN_ACT_RELU, LGNN_ACT_ELU>(act, [&](auto ACT) {
+      enqueue(k_bn_bwd_apply<ACT>, ew_grid(M, N), dim3(NT), s, dA, Z, mask, M, N, scale, shift,
+              mean, invstd, sums, count, training, dZ);
+    });
+    if (const int e = last_error()) return e;
   }
   if (dgamma || dbeta) {
-    hipLaunchKernelGGL(k_bn_param_grads, dim3((N + NT - 1) / NT), dim3(NT), 0, s, sums, N, dgamma,
-                       dbeta);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_bn_param_grads, dim3((N + NT - 1) / NT), dim3(NT), s, sums, N,
+                             dgamma, dbeta)) return e;
   }
   return LGNN_OK;
 }

@@ -19,7 +19,7 @@
 // The learning rate is a launch argument (lgnn_adam_step; fixed inside a captured graph) or a
 // device float every workgroup reads beside the step count (lgnn_adam_step_dlr, lgnn_sgd_step's
 // lr_dev), so that a scheduler's write between two replays acts on the next one.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -187,8 +187,7 @@ static int adam_step(int n, float* const* params, const float* const* grads,
   else
     hipLaunchKernelGGL(k_adam<float>, dim3(grid), dim3(kT), 0, as_stream(stream), J, step,
                        ticket, lr, beta1, beta2, eps, weight_decay, decoupled, maximize, advance);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_adam_step(int n, float* const* params, const float* const* grads,
@@ -226,9 +225,7 @@ extern "C" int lgnn_sgd_step(int n, float* const* params, const float* const* gr
                                   numels);
   if (grid == 0) return LGNN_EINVAL;
   // without momentum no step is kept: the kernel is handed none, whatever the caller passed
-  hipLaunchKernelGGL(k_sgd, dim3(grid), dim3(kT), 0, as_stream(stream), J,
-                     has_buf ? step : nullptr, has_buf ? ticket : nullptr, lr, lr_dev, momentum,
-                     dampening, weight_decay, nesterov, maximize, advance);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_sgd, dim3(grid), dim3(kT), as_stream(stream), J, has_buf ? step : nullptr,
+                has_buf ? ticket : nullptr, lr, lr_dev, momentum, dampening, weight_decay, nesterov,
+                maximize, advance);
 }

@@ -16,7 +16,7 @@
 //
 // Thread mapping of the 4-column kernels as norm.hip: 32 lanes x 4 consecutive columns cover a
 // 128-column chunk (blockIdx.y), the block's 8 half-wave row groups stride rows / segments.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -138,9 +138,8 @@ extern "C" int lgnn_edge_sub_fwd(const float* U, const float* V, const int64_t* 
   if (!workspace || workspace_bytes < lgnn_bn_workspace_bytes(E, C)) return LGNN_ENOSPC;
   const int P = row_blocks(E);
   double* part = static_cast<double*>(workspace);
-  hipLaunchKernelGGL(k_edge_sub, dim3(P, (C + 127) / 128), dim3(NT), 0, as_stream(stream), U, V,
-                     row, col, E, C, Z, part);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch(k_edge_sub, dim3(P, (C + 127) / 128), dim3(NT), as_stream(stream), U, V,
+                           row, col, E, C, Z, part)) return e;
   return lgnn_bn_partials_reduce(part, P, C, sums, nullptr, nullptr, stream);
 }
 
@@ -149,10 +148,8 @@ extern "C" int lgnn_segment_sum(const float* X, const int64_t* ptr, const int64_
   if (S < 0 || C <= 0 || (C & 3)) return LGNN_EINVAL;
   if (S == 0) return LGNN_OK;
   if (!X || !ptr || !out) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_segment_sum, seg_grid(S, RG, C, 128), dim3(NT), 0, as_stream(stream), X,
-                     ptr, perm, S, C, sign, out);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_segment_sum, seg_grid(S, RG, C, 128), dim3(NT), as_stream(stream), X, ptr, perm,
+                S, C, sign, out);
 }
 
 extern "C" int lgnn_segment_max_fwd(const float* X, const int64_t* ptr, int64_t S, int C,
@@ -160,10 +157,8 @@ extern "C" int lgnn_segment_max_fwd(const float* X, const int64_t* ptr, int64_t 
   if (S < 0 || C <= 0) return LGNN_EINVAL;
   if (S == 0) return LGNN_OK;
   if (!ptr || !out || !arg) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_segment_max_fwd, seg_grid(S, MS, C, MC), dim3(NT), 0, as_stream(stream),
-                     X, ptr, S, C, out, arg);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_segment_max_fwd, seg_grid(S, MS, C, MC), dim3(NT), as_stream(stream), X, ptr, S,
+                C, out, arg);
 }
 
 extern "C" int lgnn_segment_max_bwd(const float* dout, const int32_t* arg, const int64_t* ptr,
@@ -171,8 +166,6 @@ extern "C" int lgnn_segment_max_bwd(const float* dout, const int32_t* arg, const
   if (S < 0 || C <= 0) return LGNN_EINVAL;
   if (S == 0) return LGNN_OK;
   if (!dout || !arg || !ptr) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_segment_max_bwd, seg_grid(S, MS, C, MC), dim3(NT), 0, as_stream(stream),
-                     dout, arg, ptr, S, C, dX);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_segment_max_bwd, seg_grid(S, MS, C, MC), dim3(NT), as_stream(stream), dout, arg,
+                ptr, S, C, dX);
 }

@@ -3,7 +3,7 @@
 //
 // Replaces (reference): global_mean_pool(x, batch) gin.py:33 / gat.py:56 (PyG scatter mean =
 // sum / clamp(count, 1)), global_add_pool (NEW), out_proj nn.Linear gin.py:25.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -212,8 +212,7 @@ extern "C" int lgnn_pool_head_fwd(const float* H, const int32_t* gptr, int64_t B
     hipLaunchKernelGGL(k_pool_head_fwd, dim3((unsigned)((B + 3) / 4)), dim3(NT), 0,
                        as_stream(stream), H, gptr, B, D, pool_mean, Wout, bout, C, pooled,
                        logits);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_pool_head_bwd(const float* dlogits, const float* pooled, int64_t B, int D,
@@ -223,18 +222,14 @@ extern "C" int lgnn_pool_head_bwd(const float* dlogits, const float* pooled, int
   const int nb_dp = (dpooled && B > 0) ? (int)((B * D + HT - 1) / HT) : 0;
   const int nb_dw = dWout ? C * ((D + 63) / 64) : 0;
   if (nb_dp + nb_dw == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_head_bwd, dim3((unsigned)(nb_dp + nb_dw)), dim3(HT), 0, as_stream(stream),
-                     dlogits, pooled, B, D, Wout, C, dpooled, dWout, dbout, nb_dp);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_head_bwd, dim3((unsigned)(nb_dp + nb_dw)), dim3(HT), as_stream(stream), dlogits,
+                pooled, B, D, Wout, C, dpooled, dWout, dbout, nb_dp);
 }
 
 extern "C" int lgnn_pool_bwd(const float* dpooled, const int64_t* batch, const int32_t* gptr,
                              int64_t M, int D, int pool_mean, float* dH, void* stream) {
   if (M < 0 || D <= 0 || !dpooled || !batch || !gptr || !dH) return LGNN_EINVAL;
   if (M == 0) return LGNN_OK;
-  hipLaunchKernelGGL(k_pool_bwd, dim3((unsigned)((M * D + NT - 1) / NT)), dim3(NT), 0,
-                     as_stream(stream), dpooled, batch, gptr, M, D, pool_mean, dH);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_pool_bwd, dim3((unsigned)((M * D + NT - 1) / NT)), dim3(NT), as_stream(stream),
+                dpooled, batch, gptr, M, D, pool_mean, dH);
 }

@@ -23,7 +23,7 @@
 // Layout: pos [N][D] fp64 (D = 2 or 3), ptr [B+1] int32 graph offsets (Batch.ptr), batch [N]
 // int64 sorted. One thread per query; a block's queries are consecutive nodes, so the candidates
 // of its graphs are one contiguous node range, staged through LDS in chunks (as k_knn).
-#include "common.h"
+#include "launch.h"
 #include "geom.h"
 #include "wg.h"
 
@@ -130,16 +130,13 @@ extern "C" int lgnn_radius_count(const double* pos, int64_t N, int dims, const i
   const double r2 = r * r;  // torch_cluster squares r on the host, in double
   const int limit = loop ? max_num_neighbors : max_num_neighbors + 1;
   const dim3 grid((unsigned)((N + QT - 1) / QT));
-  if (dims == 2)
-    hipLaunchKernelGGL((k_radius<2, false>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
-                       loop, w.cnt, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((k_radius<3, false>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
-                       loop, w.cnt, nullptr, 0, nullptr);
-  LGNN_LAUNCH_CHECK();
+  one_of<3, 2>(dims, [&](auto D) {
+    enqueue(k_radius<D, false>, grid, dim3(QT), s, pos, N, batch, ptr, r2, limit, loop, w.cnt,
+            nullptr, 0, nullptr);
+  });
+  if (const int e = last_error()) return e;
   launch_exclusive_scan(w.cnt, N, w.off, s);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_radius_graph(const double* pos, int64_t N, int dims, const int64_t* batch,
@@ -155,14 +152,11 @@ extern "C" int lgnn_radius_graph(const double* pos, int64_t N, int dims, const i
   const double r2 = r * r;
   const int limit = loop ? max_num_neighbors : max_num_neighbors + 1;
   const dim3 grid((unsigned)((N + QT - 1) / QT));
-  if (dims == 2)
-    hipLaunchKernelGGL((k_radius<2, true>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
-                       loop, nullptr, w.off, num_edges, edge_index);
-  else
-    hipLaunchKernelGGL((k_radius<3, true>), grid, dim3(QT), 0, s, pos, N, batch, ptr, r2, limit,
-                       loop, nullptr, w.off, num_edges, edge_index);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<3, 2>(dims, [&](auto D) {
+    enqueue(k_radius<D, true>, grid, dim3(QT), s, pos, N, batch, ptr, r2, limit, loop, nullptr,
+            w.off, num_edges, edge_index);
+  });
+  return last_error();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -299,16 +293,13 @@ extern "C" int lgnn_radius_pairs_count(const double* x, int64_t Nx, const double
   }
   const double r2 = r * r;
   const dim3 grid((unsigned)((Ny + QT - 1) / QT));
-  if (dims == 2)
-    hipLaunchKernelGGL((k_radius_pairs<2, false>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
-                       (int)B, r2, max_num_neighbors, w.cnt, nullptr, 0, nullptr);
-  else
-    hipLaunchKernelGGL((k_radius_pairs<3, false>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
-                       (int)B, r2, max_num_neighbors, w.cnt, nullptr, 0, nullptr);
-  LGNN_LAUNCH_CHECK();
+  one_of<3, 2>(dims, [&](auto D) {
+    enqueue(k_radius_pairs<D, false>, grid, dim3(QT), s, x, y, Ny, ptr_x, ptr_y, (int)B, r2,
+            max_num_neighbors, w.cnt, nullptr, 0, nullptr);
+  });
+  if (const int e = last_error()) return e;
   launch_exclusive_scan(w.cnt, Ny, w.off, s);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_radius_pairs(const double* x, int64_t Nx, const double* y, int64_t Ny,
@@ -325,14 +316,11 @@ extern "C" int lgnn_radius_pairs(const double* x, int64_t Nx, const double* y, i
   const double r2 = r * r;
   const dim3 grid((unsigned)((Ny + QT - 1) / QT));
   hipStream_t s = as_stream(stream);
-  if (dims == 2)
-    hipLaunchKernelGGL((k_radius_pairs<2, true>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
-                       (int)B, r2, max_num_neighbors, nullptr, w.off, num_pairs, pairs);
-  else
-    hipLaunchKernelGGL((k_radius_pairs<3, true>), grid, dim3(QT), 0, s, x, y, Ny, ptr_x, ptr_y,
-                       (int)B, r2, max_num_neighbors, nullptr, w.off, num_pairs, pairs);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<3, 2>(dims, [&](auto D) {
+    enqueue(k_radius_pairs<D, true>, grid, dim3(QT), s, x, y, Ny, ptr_x, ptr_y, (int)B, r2,
+            max_num_neighbors, nullptr, w.off, num_pairs, pairs);
+  });
+  return last_error();
 }
 
 extern "C" size_t lgnn_pairs_transpose_workspace_bytes(int64_t num_candidates) {
@@ -357,15 +345,13 @@ extern "C" int lgnn_pairs_transpose(const int64_t* col, const int64_t* rowoff, i
   }
   int32_t* cnt = static_cast<int32_t*>(workspace);
   const dim3 grid((unsigned)((Nx + QT - 1) / QT));
-  hipLaunchKernelGGL(k_pairs_transpose<false>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,
-                     (int)B, Nx, cnt, nullptr, nullptr);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = launch(k_pairs_transpose<false>, grid, dim3(QT), s, col, rowoff, ptr_x, ptr_y,
+                           (int)B, Nx, cnt, nullptr, nullptr)) return e;
   launch_exclusive_scan(cnt, Nx, tptr, s);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = last_error()) return e;
   if (num_pairs > 0) {
-    hipLaunchKernelGGL(k_pairs_transpose<true>, grid, dim3(QT), 0, s, col, rowoff, ptr_x, ptr_y,
-                       (int)B, Nx, nullptr, tptr, perm);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = launch(k_pairs_transpose<true>, grid, dim3(QT), s, col, rowoff, ptr_x, ptr_y,
+                             (int)B, Nx, nullptr, tptr, perm)) return e;
   }
   return LGNN_OK;
 }

@@ -25,7 +25,7 @@
 //               lgnn_reduce_partials(_multi) (deterministic).
 #include <algorithm>
 
-#include "common.h"
+#include "launch.h"
 #include "s3_util.h"
 
 namespace lgnn_s3g {
@@ -575,10 +575,7 @@ extern "C" int lgnn_s3_weight_planes_multi(int n, const float* const* W, const i
     const int64_t total = (int64_t)128 * J.Kp[j] * J.nnb[j];
     J.boff[j + 1] = J.boff[j] + (int)std::min<int64_t>((total + 255) / 256, 512);
   }
-  hipLaunchKernelGGL(k_s3_wprep_multi, dim3((unsigned)J.boff[n]), dim3(256), 0, as_stream(stream),
-                     J);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_s3_wprep_multi, dim3((unsigned)J.boff[n]), dim3(256), as_stream(stream), J);
 }
 
 extern "C" size_t lgnn_s3_weight_planes_numel(int out_features, int in_features, int planes) {
@@ -594,10 +591,8 @@ extern "C" int lgnn_s3_weight_planes(const float* W, int rows, int cols, int tra
   const int Kp = (in + BK - 1) / BK * BK, nnb = (out + 127) / 128;
   const int64_t total = (int64_t)128 * Kp * nnb;
   const int grid = (int)std::min<int64_t>((total + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_s3_wprep, dim3(grid), dim3(256), 0, as_stream(stream), W, rows, cols,
-                     transposed, planes, Kp, nnb, Wp);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_s3_wprep, dim3(grid), dim3(256), as_stream(stream), W, rows, cols, transposed,
+                planes, Kp, nnb, Wp);
 }
 
 // Row tiling of k_s3_gemm: whole rounds of 64-row tiles over the resident slots (2 workgroups per
@@ -606,14 +601,7 @@ extern "C" int lgnn_s3_weight_planes(const float* W, int rows, int cols, int tra
 // only 64-row tiles when the caller wants per-64-row column sums. Returns grid.x, sets *n64.
 static unsigned s3g_grid(int64_t M, int K, int nblk, bool colsum, int* n64) {
   const int64_t t64 = (M + TM - 1) / TM;
-  static int slots = -1;
-  if (slots < 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      slots = 2 * cus;
-    else slots = 0;
-  }
+  const int slots = 2 * device_cus();  // 0 when the query fails: 64-row tiles only
   const int64_t per = nblk > 0 ? slots / nblk : 0;
   if (colsum || K < 512 || per < 8 || t64 <= per) {
     *n64 = (int)t64;
@@ -642,28 +630,15 @@ extern "C" int lgnn_s3_gemm(const float* A, int64_t M, int K, const uint16_t* Wp
   hipStream_t s = as_stream(stream);
   const bool v = K % 4 == 0;
   const int nck = Kp / BK;
-#define LGNN_S3G(P, V, NC) \
-  hipLaunchKernelGGL((k_s3_gemm<P, V, NC>), grid, block, 0, s, A, M, K, Wp, Kp, bias, N, Y, \
-                     colsum_part, n64)
-#define LGNN_S3G_N(P, V)                 \
-  switch (nck) {                         \
-    case 2: LGNN_S3G(P, V, 2); break;    \
-    case 4: LGNN_S3G(P, V, 4); break;    \
-    case 8: LGNN_S3G(P, V, 8); break;    \
-    case 17: LGNN_S3G(P, V, 17); break;  \
-    default: LGNN_S3G(P, V, 0); break;   \
-  }
+  int r = LGNN_OK;
   // the unrolled bodies: K <= 128 / 256 / 512 (lins and their dX) and 1025..1088 (the
   // reference in_proj); other widths run the pair loop
-  if (planes == 3) {
-    if (v) { LGNN_S3G_N(3, true) } else { LGNN_S3G_N(3, false) }
-  } else {
-    if (v) { LGNN_S3G_N(1, true) } else { LGNN_S3G_N(1, false) }
-  }
-#undef LGNN_S3G_N
-#undef LGNN_S3G
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  one_of<1, 3>(planes, [&](auto P) { one_of<false, true>(v, [&](auto V) {
+    one_of<0, 2, 4, 8, 17>(nck, [&](auto NC) {
+      r = launch(k_s3_gemm<P, V, NC>, grid, block, s, A, M, K, Wp, Kp, bias, N, Y, colsum_part,
+                 n64, AttOut{});
+    }); }); });
+  return r;
 }
 
 // Y = act(A B^T + b) (act = LGNN_ACT_ELU: torch's ELU in the epilogue, as the tile kernels)
@@ -683,20 +658,12 @@ extern "C" int lgnn_s3_gemm_act(const float* A, int64_t M, int K, const uint16_t
   hipStream_t s = as_stream(stream);
   const bool v = K % 4 == 0;
   const int nck = Kp / BK;
-#define LGNN_S3E(V, NC)                                                                          \
-  hipLaunchKernelGGL((k_s3_gemm<3, V, NC, false, LGNN_ACT_ELU>), grid, block, 0, s, A, M, K, Wp, \
-                     Kp, bias, N, Y, nullptr, n64)
-#define LGNN_S3E_N(V)                  \
-  switch (nck) {                       \
-    case 2: LGNN_S3E(V, 2); break;     \
-    case 8: LGNN_S3E(V, 8); break;     \
-    default: LGNN_S3E(V, 0); break;    \
-  }
-  if (v) { LGNN_S3E_N(true) } else { LGNN_S3E_N(false) }
-#undef LGNN_S3E_N
-#undef LGNN_S3E
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_OK;
+  one_of<false, true>(v, [&](auto V) { one_of<0, 2, 8>(nck, [&](auto NC) {
+    r = launch(k_s3_gemm<3, V, NC, false, LGNN_ACT_ELU>, grid, block, s, A, M, K, Wp, Kp, bias, N,
+               Y, nullptr, n64, AttOut{});
+  }); });
+  return r;
 }
 
 extern "C" int lgnn_s3_gemm_att(const float* A, int64_t M, int K, const uint16_t* Wp, int N,
@@ -716,20 +683,12 @@ extern "C" int lgnn_s3_gemm_att(const float* A, int64_t M, int K, const uint16_t
   const AttOut at{att_src, att_dst, a_s, a_d, heads, C};
   const bool v = K % 4 == 0;
   const int nck = Kp / BK;
-#define LGNN_S3A(P, V, NC)                                                                      \
-  hipLaunchKernelGGL((k_s3_gemm<P, V, NC, true>), grid, block, 0, s, A, M, K, Wp, Kp, nullptr, N, \
-                     Y, nullptr, n64, at)
-#define LGNN_S3A_N(P, V)                 \
-  switch (nck) {                         \
-    case 2: LGNN_S3A(P, V, 2); break;    \
-    case 17: LGNN_S3A(P, V, 17); break;  \
-    default: LGNN_S3A(P, V, 0); break;   \
-  }
-  if (v) { LGNN_S3A_N(3, true) } else { LGNN_S3A_N(3, false) }
-#undef LGNN_S3A_N
-#undef LGNN_S3A
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_OK;
+  one_of<false, true>(v, [&](auto V) { one_of<0, 2, 17>(nck, [&](auto NC) {
+    r = launch(k_s3_gemm<3, V, NC, true>, grid, block, s, A, M, K, Wp, Kp, nullptr, N, Y, nullptr,
+               n64, at);
+  }); });
+  return r;
 }
 
 // k_s3_wgrad2: 32-row chunks per split, so that the grid (128-wide k-blocks x splits x n-blocks)
@@ -761,12 +720,9 @@ extern "C" int lgnn_s3_wgrad(const float* dY, int N, const float* X, int64_t M, 
   const int nkb = (K + 127) / 128, cps = s3_wg_cps(M, K, N);
   const dim3 grid((unsigned)(nkb * num_partials), (unsigned)((N + 127) / 128)), block(NT);
   hipStream_t s = as_stream(stream);
-  if (planes == 3)
-    hipLaunchKernelGGL((k_s3_wgrad2<3>), grid, block, 0, s, dY, N, X, M, K, nkb, cps, partials,
-                       db_partials);
-  else
-    hipLaunchKernelGGL((k_s3_wgrad2<1>), grid, block, 0, s, dY, N, X, M, K, nkb, cps, partials,
-                       db_partials);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  int r = LGNN_OK;
+  one_of<1, 3>(planes, [&](auto P) {
+    r = launch(k_s3_wgrad2<P>, grid, block, s, dY, N, X, M, K, nkb, cps, partials, db_partials);
+  });
+  return r;
 }

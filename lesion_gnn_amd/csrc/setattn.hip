@@ -17,7 +17,7 @@
 // and one fixed summation order: no atomics, two runs agree bit for bit.
 // The products run on the fp32 VALU (fmaf chains): on gfx950 the fp32 MFMA has the VALU's rate,
 // and bf16 operands would not hold the 1e-4 bar without a split.
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 namespace lgnn_setattn {
@@ -562,10 +562,8 @@ extern "C" int lgnn_set_attn_mask_offsets(const int32_t* qptr, int q_rows, const
                                           int64_t* mask_off, void* stream) {
   if (num_sets < 0 || heads < 1 || !mask_off || (!qptr && q_rows < 0) || (!kptr && k_rows < 0))
     return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_mask_offsets, dim3(1), dim3(kThreads), 0, as_stream(stream), qptr, q_rows,
-                     kptr, k_rows, num_sets, heads, mask_off);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_mask_offsets, dim3(1), dim3(kThreads), as_stream(stream), qptr, q_rows, kptr,
+                k_rows, num_sets, heads, mask_off);
 }
 
 extern "C" int lgnn_set_attn_fwd(const float* q, int64_t ldq, const float* k, int64_t ldk,
@@ -580,10 +578,8 @@ extern "C" int lgnn_set_attn_fwd(const float* q, int64_t ldq, const float* k, in
   const Args a = make_args(q, ldq, k, ldk, v, ldv, qptr, q_rows, q_shared, kptr, k_rows, heads,
                            head_dim, mask, mask_off);
   const size_t lds = ((size_t)(QB + 2 * KB) * (head_dim + 1) + QB * PLD) * sizeof(float);
-  hipLaunchKernelGGL(k_attn_fwd, dim3((unsigned)num_sets, heads, kSplit), dim3(kThreads), lds,
-                     as_stream(stream), a, out, lse);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch_lds(k_attn_fwd, dim3((unsigned)num_sets, heads, kSplit), dim3(kThreads), lds,
+                    as_stream(stream), a, out, lse);
 }
 
 extern "C" int lgnn_set_attn_bwd(const float* q, int64_t ldq, const float* k, int64_t ldk,
@@ -602,13 +598,10 @@ extern "C" int lgnn_set_attn_bwd(const float* q, int64_t ldq, const float* k, in
   const size_t lds =
       ((size_t)(2 * QB + 2 * KB) * (head_dim + 1) + 2 * QB * PLD + 2 * QB) * sizeof(float);
   const dim3 grid((unsigned)num_sets, heads, kSplit);
-  hipLaunchKernelGGL(k_attn_bwd_dkv, grid, dim3(kThreads), lds, as_stream(stream), a, out, dout,
-                     lse, dk, lddk, dv, lddv);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_attn_bwd_dq, grid, dim3(kThreads), lds - QB * PLD * sizeof(float),
-                     as_stream(stream), a, out, dout, lse, dq, lddq);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  if (const int e = launch_lds(k_attn_bwd_dkv, grid, dim3(kThreads), lds, as_stream(stream), a, out,
+                               dout, lse, dk, lddk, dv, lddv)) return e;
+  return launch_lds(k_attn_bwd_dq, grid, dim3(kThreads), lds - QB * PLD * sizeof(float),
+                    as_stream(stream), a, out, dout, lse, dq, lddq);
 }
 
 extern "C" int lgnn_res_norm_fwd(const float* a, int a_rows, const float* b, int act,
@@ -623,10 +616,8 @@ extern "C" int lgnn_res_norm_fwd(const float* a, int a_rows, const float* b, int
   if (a_rows > 0 && !a) return LGNN_EINVAL;
   if (!b || !y) return LGNN_EINVAL;
   const unsigned grid = (unsigned)((M + kRowsPerBlock - 1) / kRowsPerBlock);
-  hipLaunchKernelGGL(k_res_norm_fwd, dim3(grid), dim3(kThreads), 0, as_stream(stream), a, a_rows,
-                     b, act, gamma, beta, eps, M, C, y, mean, rstd);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_res_norm_fwd, dim3(grid), dim3(kThreads), as_stream(stream), a, a_rows, b, act,
+                gamma, beta, eps, M, C, y, mean, rstd);
 }
 
 extern "C" int lgnn_res_norm_bwd_partials(int64_t M) {
@@ -654,11 +645,8 @@ extern "C" int lgnn_res_norm_bwd(const float* a, int a_rows, const float* b, int
   }
   if (!b || !dy) return LGNN_EINVAL;
   const int64_t rows_per = (M + num_partials - 1) / num_partials;
-  hipLaunchKernelGGL(k_res_norm_bwd, dim3(num_partials), dim3(kThreads), 0, as_stream(stream), a,
-                     a_rows, b, act, gamma, M, C, mean, rstd, dy, da, db, gamma ? part : nullptr,
-                     rows_per);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_res_norm_bwd, dim3(num_partials), dim3(kThreads), as_stream(stream), a, a_rows, b,
+                act, gamma, M, C, mean, rstd, dy, da, db, gamma ? part : nullptr, rows_per);
 }
 
 extern "C" int lgnn_set_readout_fwd(const float* x, const int32_t* gptr, int64_t num_sets,
@@ -667,10 +655,8 @@ extern "C" int lgnn_set_readout_fwd(const float* x, const int32_t* gptr, int64_t
   const int64_t n = num_sets * (mean ? (int64_t)C : (int64_t)rows * C);
   if (n == 0) return LGNN_OK;
   if (!x || !out || n > 2147483647LL * kThreads) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_readout_fwd, dim3((unsigned)((n + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, as_stream(stream), x, gptr, n, rows, C, mean, out);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_readout_fwd, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads),
+                as_stream(stream), x, gptr, n, rows, C, mean, out);
 }
 
 extern "C" int lgnn_set_readout_bwd(const float* dout, const int32_t* gptr, int64_t num_sets,
@@ -679,18 +665,14 @@ extern "C" int lgnn_set_readout_bwd(const float* dout, const int32_t* gptr, int6
   const int64_t n = num_sets * rows * C;
   if (n == 0) return LGNN_OK;
   if (!dout || !dx || n > 2147483647LL * kThreads) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_readout_bwd, dim3((unsigned)((n + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, as_stream(stream), dout, gptr, n, rows, C, mean, dx);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_readout_bwd, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads),
+                as_stream(stream), dout, gptr, n, rows, C, mean, dx);
 }
 
 extern "C" int lgnn_add(const float* a, const float* b, float* y, int64_t n, void* stream) {
   if (n < 0 || n > 2147483647LL * kThreads) return LGNN_EINVAL;
   if (n == 0) return LGNN_OK;
   if (!a || !b || !y) return LGNN_EINVAL;
-  hipLaunchKernelGGL(k_add, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     as_stream(stream), a, b, y, n);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_add, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads),
+                as_stream(stream), a, b, y, n);
 }

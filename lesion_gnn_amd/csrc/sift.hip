@@ -21,7 +21,7 @@
 // give the same bits. Every loop is bounded and every write is checked against its capacity.
 #include <math.h>
 
-#include "common.h"
+#include "launch.h"
 #include "wg.h"
 
 #pragma clang fp contract(off)
@@ -819,7 +819,7 @@ extern "C" int lgnn_sift_pyramid(const uint8_t* image, int batch, int height, in
   hipStream_t st = as_stream(stream);
   const int64_t npix = (int64_t)batch * height * width;
   k_gray<<<(unsigned)((npix + 255) / 256), 256, 0, st>>>(image, npix, channels, gray);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = last_error()) return e;
   Taps taps[kLevels];
   make_taps(base_sigma(sigma), &taps[0]);
   for (int i = 1; i < kLevels; ++i) make_taps(level_sigma(sigma, i), &taps[i]);
@@ -838,12 +838,12 @@ extern "C" int lgnn_sift_pyramid(const uint8_t* image, int batch, int height, in
           gauss + oc.goff[o - 1] + (int64_t)kLayers * ph * pw, (int64_t)kLevels * ph * pw, pw, g,
           kLevels * plane, h, w);
     }
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     for (int i = 1; i < kLevels; ++i) {
       k_blur<false><<<grid, 256, 0, st>>>(g + (i - 1) * plane, kLevels * plane, g + i * plane,
                                           kLevels * plane, d + (i - 1) * plane, kDogs * plane, h,
                                           w, taps[i]);
-      LGNN_LAUNCH_CHECK();
+      if (const int e = last_error()) return e;
     }
   }
   return LGNN_OK;
@@ -864,11 +864,10 @@ extern "C" int lgnn_sift_count(const float* dog, int batch, int height, int widt
   hipStream_t st = as_stream(stream);
   if (rows) {
     k_extrema<false><<<(rows + 3) / 4, 256, 0, st>>>(dog, oc, rows, counts, nullptr, nullptr, 0);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
   }
   launch_exclusive_scan(counts, rows, row_ptr, st);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_sift_candidates(const float* dog, int batch, int height, int width,
@@ -882,8 +881,7 @@ extern "C" int lgnn_sift_candidates(const float* dog, int batch, int height, int
   if (!dog) return LGNN_EINVAL;
   k_extrema<true><<<(rows + 3) / 4, 256, 0, as_stream(stream)>>>(dog, oc, rows, nullptr, row_ptr,
                                                                 cand, capacity);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" size_t lgnn_sift_keypoints_workspace_bytes(int batch, int num_candidates) {
@@ -907,31 +905,30 @@ extern "C" int lgnn_sift_keypoints(const float* gauss, const float* dog, int bat
   const KeypointWs ws = keypoint_ws(workspace, batch, n > 0 ? n : 1);
   if (n) {
     k_refine<<<(n + 63) / 64, 64, 0, st>>>(dog, oc, batch, sigma, cand, n, ws.ref);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     k_orient<<<n, 64, 0, st>>>(gauss, oc, batch, cand, ws.ref, n, ws.npk, ws.angles);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
   }
   launch_exclusive_scan(ws.npk, n, ws.koff, st);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = last_error()) return e;
   k_ranges<<<(batch + 256) / 256, 256, 0, st>>>(cand, n, ws.koff, batch, ws.kstart, ws.thr,
                                                 ws.kept);
-  LGNN_LAUNCH_CHECK();
+  if (const int e = last_error()) return e;
   if (n) {
     k_flatten<<<(n + 63) / 64, 64, 0, st>>>(cand, ws.ref, ws.npk, ws.koff, ws.angles, n, cap,
                                             ws.kp);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     const int blocks = (cap + 63) / 64;
     k_dedupe<<<blocks, 64, 0, st>>>(ws.kp, ws.kstart, batch, cap, ws.alive);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     k_rank<<<blocks, 64, 0, st>>>(ws.kp, ws.kstart, batch, cap, ws.alive, num_keypoints, ws.rank,
                                   ws.thr);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
     k_keep<<<blocks, 64, 0, st>>>(ws.kp, ws.kstart, batch, cap, ws.alive, ws.thr, ws.kept);
-    LGNN_LAUNCH_CHECK();
+    if (const int e = last_error()) return e;
   }
   launch_exclusive_scan(ws.kept, batch, node_ptr, st);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_sift_gather(int batch, int num_candidates, const int64_t* node_ptr,
@@ -948,8 +945,7 @@ extern "C" int lgnn_sift_gather(int batch, int num_candidates, const int64_t* no
   k_gather<<<(cap + 63) / 64, 64, 0, as_stream(stream)>>>(ws.kp, ws.kstart, batch, cap, ws.alive,
                                                          ws.rank, ws.thr, node_ptr, total_nodes,
                                                          kf, ki);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }
 
 extern "C" int lgnn_sift_descriptors(const float* gauss, int batch, int height, int width,
@@ -960,6 +956,5 @@ extern "C" int lgnn_sift_descriptors(const float* gauss, int batch, int height, 
   if (!gauss || !kf || !ki || !x) return LGNN_EINVAL;
   const Octaves oc = octaves(batch, height, width);
   k_descriptors<<<num_nodes, 64, 0, as_stream(stream)>>>(gauss, oc, batch, kf, ki, num_nodes, x);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return last_error();
 }

@@ -15,7 +15,7 @@
 // Bound: HBM (reads x once for the min, k rows per graph + its keys; writes B*k*D + M ints).
 // The key ranking is O(n_g^2) LDS compares per graph (n_g <= 512 for lesion graphs: 1k compares
 // per thread), not on the critical path at these sizes.
-#include "common.h"
+#include "launch.h"
 
 namespace lgnn_sortpool {
 
@@ -143,12 +143,9 @@ extern "C" int lgnn_sort_pool_fwd(const float* x, int64_t num_nodes, int dims,
   float* part = static_cast<float*>(workspace);
   const int64_t n = num_nodes * dims;
   const int blocks = (int)std::min<int64_t>(kMinBlocks, std::max<int64_t>(1, (n + kThreads - 1) / kThreads));
-  hipLaunchKernelGGL(k_min_partials, dim3(blocks), dim3(kThreads), 0, s, x, n, part);
-  LGNN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sort_pool, dim3((unsigned)num_graphs), dim3(kThreads), 0, s, x, dims, gptr,
-                     k, part, blocks, out, rank, fill);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  if (const int e = launch(k_min_partials, dim3(blocks), dim3(kThreads), s, x, n, part)) return e;
+  return launch(k_sort_pool, dim3((unsigned)num_graphs), dim3(kThreads), s, x, dims, gptr, k, part,
+                blocks, out, rank, fill);
 }
 
 extern "C" int lgnn_sort_pool_bwd(const float* dout, const float* x, const int32_t* rank,
@@ -159,8 +156,6 @@ extern "C" int lgnn_sort_pool_bwd(const float* dout, const float* x, const int32
   if (!dout || !x || !rank || !batch || !fill || !dx) return LGNN_EINVAL;
   const int64_t total = num_nodes * dims;
   const int blocks = (int)std::min<int64_t>(4096, (total + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(k_sort_pool_bwd, dim3(blocks), dim3(kThreads), 0, as_stream(stream), dout,
-                     x, rank, batch, fill, num_nodes, dims, k, dx);
-  LGNN_LAUNCH_CHECK();
-  return LGNN_OK;
+  return launch(k_sort_pool_bwd, dim3(blocks), dim3(kThreads), as_stream(stream), dout, x, rank,
+                batch, fill, num_nodes, dims, k, dx);
 }

@@ -23,7 +23,7 @@
 // Feature index order: the planes store feature k at position perm16(k) (bits 2 and 3 of k
 // swapped), which is the k order an MFMA accumulator hands to the next MFMA; weights, images and
 // accumulators all use it, so every product pairs equal k.
-#include "common.h"
+#include "launch.h"
 #include "tile.h"
 #include "tile_util.h"
 #include "s3_util.h"
@@ -447,54 +447,25 @@ extern "C" int lgnn_s3_debug_stamps(unsigned long long* host_out) {
 }
 #endif
 
-hipError_t lgnn_s3_fbwd_occupancy(int* per_cu);  // stack3_bwd.hip
+int lgnn_s3_fbwd_capacity();  // stack3_bwd.hip
 
-// Workgroups of a fused stack kernel that can be resident on this device at once (occupancy
-// per CU x CU count), cached per device and variant: slot 0..3 the forward k_s3_fwd<mode>, 4 the
-// backward (k_s3_fbwd<3, true>). A negative value is a HIP error code.
-static int fused_capacity(int slot) {
-  static int cache[5][16];
-  static bool have[5][16];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return -(int)hipErrorInvalidDevice;
-  if (have[slot][dev]) return cache[slot][dev];
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return -(int)hipGetLastError();
-  hipError_t e;
-  switch (slot) {
-    case 0:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<0>,
-                                                       lgnn_tile::NT, 0);
-      break;
-    case 1:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<1>,
-                                                       lgnn_tile::NT, 0);
-      break;
-    case 2:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<2>,
-                                                       lgnn_tile::NT, 0);
-      break;
-    case 3:
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lgnn_s3::k_s3_fwd<3>,
-                                                       lgnn_tile::NT, 0);
-      break;
-    default:
-      e = lgnn_s3_fbwd_occupancy(&per_cu);
-  }
-  if (e != hipSuccess) return -(int)e;
-  cache[slot][dev] = cus * per_cu;
-  have[slot][dev] = true;
-  return cache[slot][dev];
+// Workgroups of the fused forward k_s3_fwd<mode> that can be resident on this device at once
+// (resident_workgroups, launch.h). A negative value is a HIP error code, negated.
+static int fused_capacity(int mode) {
+  int cap = 0;
+  one_of<LGNN_S3_FWD_FOLD_H0, 0, 1, LGNN_S3_FWD_FOLD>(mode, [&](auto MODE) {
+    cap = resident_workgroups<lgnn_s3::k_s3_fwd<MODE>>(lgnn_tile::NT);
+  });
+  return cap;
 }
 
 // which = 0: the forward — the smallest over its variants, so a grid that fits runs in every
-// mode (the launch itself checks its own variant's); 1: the backward.
+// mode (the launch itself checks its own variant's); 1: the backward (k_s3_fbwd<3, true>).
 extern "C" int lgnn_fused_grid_capacity(int which) {
   if (which < 0 || which > 1) return LGNN_EINVAL;
-  if (which == 1) return fused_capacity(4);
+  if (which == 1) return lgnn_s3_fbwd_capacity();
   int cap = 0;
-  for (int m = 0; m < 4; ++m) {
+  for (int m = 0; m <= LGNN_S3_FWD_FOLD_H0; ++m) {
     const int c = fused_capacity(m);
     if (c < 0) return c;
     cap = m == 0 || c < cap ? c : cap;
@@ -516,37 +487,7 @@ extern "C" int lgnn_weight_planes(int nl, const float* const* W, const int* widt
   const int r = lgnn_s3::plane_args(nl, W, widths, planes, planes_t, a);
   if (r != LGNN_OK) return r;
   const int threads = lgnn_s3::plane_items(a);
-  hipLaunchKernelGGL(lgnn_s3::k_wplanes, dim3((threads + 255) / 256), dim3(256), 0,
-                     as_stream(stream), a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
-}
-
-static int stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
-                        const int32_t* rowptr, const int32_t* col, const float* w, int L,
-                        const uint16_t* planes, const float* const* b, const int* widths,
-                        float* const* H, const int32_t* tile_open, const float* const* Wf,
-                        float* const* S, int32_t* sync, void* adjt, void* stream);
-
-extern "C" int lgnn_gcn_stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
-                                     const int32_t* rowptr, const int32_t* col, const float* w,
-                                     int L, const uint16_t* planes, const float* const* b,
-                                     const int* widths, float* const* H,
-                                     const int32_t* tile_open, void* adjt, void* stream) {
-  return stack_fwd_s3(X, M, d_in, has_in_proj, rowptr, col, w, L, planes, b, widths, H, tile_open,
-                      nullptr, nullptr, nullptr, adjt, stream);
-}
-
-extern "C" int lgnn_gcn_stack_fwd_s3_all(const float* X, int64_t M, int d_in, int has_in_proj,
-                                         const int32_t* rowptr, const int32_t* col,
-                                         const float* w, int L, const uint16_t* planes,
-                                         const float* const* W, const float* const* b,
-                                         const int* widths, float* const* H, float* const* S,
-                                         int32_t* tile_open, void* adjt, void* stream) {
-  if (!W || !S || !tile_open || M < 0) return LGNN_EINVAL;
-  const int64_t ntiles = (M + lgnn_tile::TM - 1) / lgnn_tile::TM;
-  return stack_fwd_s3(X, M, d_in, has_in_proj, rowptr, col, w, L, planes, b, widths, H, tile_open,
-                      W, S, tile_open + ntiles + 1, adjt, stream);
+  return launch(lgnn_s3::k_wplanes, dim3((threads + 255) / 256), dim3(256), as_stream(stream), a);
 }
 
 static int stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
@@ -592,23 +533,31 @@ static int stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
     if (cap < (int)grid.x) return cap == LGNN_EINVAL ? cap : cap < 0 ? -cap : LGNN_EBUSY;
   }
   hipStream_t s = as_stream(stream);
-  switch (has_in_proj) {
-    case 0:
-      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<0>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr, col,
-                         w, L, a, planes, tile_open, o);
-      break;
-    case 1:
-      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<1>, grid, dim3(lgnn_tile::NT), 0, s, X, M, rowptr, col,
-                         w, L, a, planes, tile_open, o);
-      break;
-    case LGNN_S3_FWD_FOLD:
-      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<LGNN_S3_FWD_FOLD>, grid, dim3(lgnn_tile::NT), 0, s, X,
-                         M, rowptr, col, w, L, a, planes, tile_open, o);
-      break;
-    default:
-      hipLaunchKernelGGL(lgnn_s3::k_s3_fwd<LGNN_S3_FWD_FOLD_H0>, grid, dim3(lgnn_tile::NT), 0, s,
-                         X, M, rowptr, col, w, L, a, planes, tile_open, o);
-  }
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_OK;
+  one_of<LGNN_S3_FWD_FOLD_H0, 0, 1, LGNN_S3_FWD_FOLD>(has_in_proj, [&](auto MODE) {
+    r = launch(lgnn_s3::k_s3_fwd<MODE>, grid, dim3(lgnn_tile::NT), s, X, M, rowptr, col, w, L, a,
+               planes, tile_open, o);
+  });
+  return r;
+}
+
+extern "C" int lgnn_gcn_stack_fwd_s3(const float* X, int64_t M, int d_in, int has_in_proj,
+                                     const int32_t* rowptr, const int32_t* col, const float* w,
+                                     int L, const uint16_t* planes, const float* const* b,
+                                     const int* widths, float* const* H,
+                                     const int32_t* tile_open, void* adjt, void* stream) {
+  return stack_fwd_s3(X, M, d_in, has_in_proj, rowptr, col, w, L, planes, b, widths, H, tile_open,
+                      nullptr, nullptr, nullptr, adjt, stream);
+}
+
+extern "C" int lgnn_gcn_stack_fwd_s3_all(const float* X, int64_t M, int d_in, int has_in_proj,
+                                         const int32_t* rowptr, const int32_t* col,
+                                         const float* w, int L, const uint16_t* planes,
+                                         const float* const* W, const float* const* b,
+                                         const int* widths, float* const* H, float* const* S,
+                                         int32_t* tile_open, void* adjt, void* stream) {
+  if (!W || !S || !tile_open || M < 0) return LGNN_EINVAL;
+  const int64_t ntiles = (M + lgnn_tile::TM - 1) / lgnn_tile::TM;
+  return stack_fwd_s3(X, M, d_in, has_in_proj, rowptr, col, w, L, planes, b, widths, H, tile_open,
+                      W, S, tile_open + ntiles + 1, adjt, stream);
 }

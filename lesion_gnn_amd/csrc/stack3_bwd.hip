@@ -19,7 +19,7 @@
 // forward's GEMM1 with the transposed weight planes (k_wplanes WpT). dZ_{l-1} goes to HBM in P
 // layout (feature on the lane: 128-B row segments) for the next launch.
 #include <cstdlib>
-#include "common.h"
+#include "launch.h"
 #include "tile.h"
 #include "tile_util.h"
 #include "s3_util.h"
@@ -450,17 +450,12 @@ extern "C" int lgnn_gcn_stack_bwd_s3(const float* dP, const int64_t* batch, cons
       a.dZout = dz[(L - l) & 1];
       a.elu_prev = l >= 2;
     }
-    if (l == L)
-      hipLaunchKernelGGL(lgnn_s3::k_s3_bwd<lgnn_s3::BM_POOL>, grid, blk, 0, s, rowptr, col, w, M,
-                         a, tile_open);
-    else if (l >= 1)
-      hipLaunchKernelGGL(lgnn_s3::k_s3_bwd<lgnn_s3::BM_CONV>, grid, blk, 0, s, rowptr, col, w, M,
-                         a, tile_open);
-    else
-      hipLaunchKernelGGL(lgnn_s3::k_s3_bwd<lgnn_s3::BM_LIN>, grid, blk, 0, s, rowptr, col, w, M,
-                         a, tile_open);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    using namespace lgnn_s3;
+    int r = LGNN_OK;
+    one_of<BM_LIN, BM_POOL, BM_CONV>(l == L ? BM_POOL : l >= 1 ? BM_CONV : BM_LIN, [&](auto BM) {
+      r = launch(k_s3_bwd<BM>, grid, blk, s, rowptr, col, w, M, a, tile_open);
+    });
+    if (r != LGNN_OK) return r;
   }
   return LGNN_OK;
 }
@@ -1620,46 +1615,29 @@ static int stack_bwd_s3f(const float* dP, const int64_t* batch, const int32_t* g
     const int cap = lgnn_fused_grid_capacity(1);
     if (cap < (int)grid.x) return cap == LGNN_EINVAL ? cap : cap < 0 ? -cap : LGNN_EBUSY;
   }
-  if (L == 3 && adjt)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<4, true, true>), grid, blk, 0, s, rowptr, col, w, M, a,
-                       tile_open, o);
-  else if (L == 3)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<4, false, true>), grid, blk, 0, s, rowptr, col, w, M,
-                       a, tile_open, o);
-  else if (defer && L == 1 && adjt)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, true, false, true>), grid, blk, 0, s, rowptr, col,
-                       w, M, a, tile_open, o);
-  else if (defer && L == 1)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, false, false, true>), grid, blk, 0, s, rowptr, col,
-                       w, M, a, tile_open, o);
-  else if (defer && adjt)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, true, false, true>), grid, blk, 0, s, rowptr, col,
-                       w, M, a, tile_open, o);
-  else if (defer)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, false, false, true>), grid, blk, 0, s, rowptr, col,
-                       w, M, a, tile_open, o);
-  else if (L == 1 && adjt)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, true>), grid, blk, 0, s, rowptr, col, w, M, a,
-                       tile_open, o);
-  else if (L == 1)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<2, false>), grid, blk, 0, s, rowptr, col, w, M, a,
-                       tile_open, o);
-  else if (adjt)
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, true>), grid, blk, 0, s, rowptr, col, w, M, a,
-                       tile_open, o);
+  int r = LGNN_OK;
+  const bool ag = adjt != nullptr;
+  if (L == 3)  // XIN: takes dZ_0, and never defers (defer needs L <= 2)
+    one_of<false, true>(ag, [&](auto AG) {
+      r = launch(lgnn_s3::k_s3_fbwd<4, AG, true>, grid, blk, s, rowptr, col, w, M, a, tile_open, o);
+    });
   else
-    hipLaunchKernelGGL((lgnn_s3::k_s3_fbwd<3, false>), grid, blk, 0, s, rowptr, col, w, M, a,
-                       tile_open, o);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+    one_of<false, true>(defer, [&](auto DF) { one_of<3, 2>(L + 1, [&](auto NL) {
+      one_of<false, true>(ag, [&](auto AG) {
+        r = launch(lgnn_s3::k_s3_fbwd<NL, AG, false, DF>, grid, blk, s, rowptr, col, w, M, a,
+                   tile_open, o);
+      }); }); });
+  return r;
 }
 
-// workgroups per CU of the fused backward (the open-tile phase's grid barrier needs them all
-// resident)
-hipError_t lgnn_s3_fbwd_occupancy(int* per_cu) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, lgnn_s3::k_s3_fbwd<3, true>,
-                                                      lgnn_tile::NT, 0);
+// workgroups of the fused backward the device keeps resident (the open-tile phase's grid barrier
+// needs them all resident); negative: a HIP error code, negated. (A template, so that the launch
+// above stays the kernel's first use: the code object lists its kernels in that order.)
+template <bool AG>
+static int fbwd_capacity() {
+  return resident_workgroups<lgnn_s3::k_s3_fbwd<3, AG>>(lgnn_tile::NT);
 }
+int lgnn_s3_fbwd_capacity() { return fbwd_capacity<true>(); }
 
 #ifdef LGNN_STAMPS
 extern "C" int lgnn_debug_stamps_s3b(unsigned long long* host_out) {

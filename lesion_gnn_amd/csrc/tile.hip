@@ -11,7 +11,7 @@
 //    streams S instead of re-gathering;
 //  * outputs are staged through LDS and written as whole 512-B rows;
 //  * persistent grid (2 workgroups per CU) with the weight fragment loaded once per workgroup.
-#include "common.h"
+#include "launch.h"
 #include "tile.h"
 #include "tile_util.h"
 #include "tile_lw.h"
@@ -660,56 +660,39 @@ int lgnn_tile_partials(int64_t M) {
   return (int)(p < 1 ? 1 : p);
 }
 
-hipError_t lgnn_tile_fwd(hipStream_t s, const float* X, int64_t M, int K, const int32_t* rowptr,
-                         const int32_t* col, const float* w, float self_scale, const float* W,
-                         const float* b, int N, int act, float* Y, float* S_out,
-                         const int32_t* tile_mask, int want) {
+int lgnn_tile_fwd(hipStream_t s, const float* X, int64_t M, int K, const int32_t* rowptr,
+                  const int32_t* col, const float* w, float self_scale, const float* W,
+                  const float* b, int N, int act, float* Y, float* S_out, const int32_t* tile_mask,
+                  int want) {
   const int64_t ntiles = (M + TM - 1) / TM;
   dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));
-#define LGNN_TF(G, A)                                                                         \
-  hipLaunchKernelGGL((k_fwd<G, A>), grid, dim3(NT), 0, s, X, M, K, rowptr, col, w, self_scale, \
-                     W, b, N, Y, S_out, tile_mask, want, BnFuse{})
-  if (rowptr) {
-    if (act == LGNN_ACT_ELU) LGNN_TF(true, LGNN_ACT_ELU);
-    else LGNN_TF(true, LGNN_ACT_NONE);
-  } else {
-    if (act == LGNN_ACT_ELU) LGNN_TF(false, LGNN_ACT_ELU);
-    else LGNN_TF(false, LGNN_ACT_NONE);
-  }
-#undef LGNN_TF
-  return hipGetLastError();
+  one_of<false, true>(rowptr != nullptr, [&](auto G) {
+    one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+      enqueue(k_fwd<G, A>, grid, dim3(NT), s, X, M, K, rowptr, col, w, self_scale, W, b, N, Y,
+              S_out, tile_mask, want, BnFuse{});
+    });
+  });
+  return last_error();
 }
 
-hipError_t lgnn_tile_bwd(hipStream_t s, int grad_mode, const float* dY, const int64_t* batch,
-                         const int32_t* gptr, int pool_mean, const int32_t* tptr,
-                         const int32_t* tidx, const float* tw, float tself, const float* H,
-                         int act, const float* X, int64_t M, int K, const float* W, int N,
-                         float* dXpre, float* dWp, float* dbp, int P, const int32_t* tile_mask,
-                         int want, int accumulate) {
+int lgnn_tile_bwd(hipStream_t s, int grad_mode, const float* dY, const int64_t* batch,
+                  const int32_t* gptr, int pool_mean, const int32_t* tptr, const int32_t* tidx,
+                  const float* tw, float tself, const float* H, int act, const float* X, int64_t M,
+                  int K, const float* W, int N, float* dXpre, float* dWp, float* dbp, int P,
+                  const int32_t* tile_mask, int want, int accumulate) {
   dim3 grid((unsigned)P);
-#define LGNN_TB(GM, AC, D)                                                                     \
-  hipLaunchKernelGGL((k_bwd<GM, AC, D>), grid, dim3(NT), 0, s, dY, batch, gptr, pool_mean, tptr, \
-                     tidx, tw, tself, H, X, M, K, W, N, dXpre, dWp, dbp, tile_mask, want,        \
-                     accumulate, BnFuse{})
-#define LGNN_TB_D(GM, AC) \
-  if (dXpre) LGNN_TB(GM, AC, true); else LGNN_TB(GM, AC, false);
-  if (act == LGNN_ACT_ELU) {
-    if (grad_mode == LGNN_GRAD_DIRECT) { LGNN_TB_D(LGNN_GRAD_DIRECT, LGNN_ACT_ELU) }
-    else if (grad_mode == LGNN_GRAD_POOL) { LGNN_TB_D(LGNN_GRAD_POOL, LGNN_ACT_ELU) }
-    else { LGNN_TB_D(LGNN_GRAD_TRANSPOSE, LGNN_ACT_ELU) }
-  } else {
-    if (grad_mode == LGNN_GRAD_DIRECT) { LGNN_TB_D(LGNN_GRAD_DIRECT, LGNN_ACT_NONE) }
-    else if (grad_mode == LGNN_GRAD_POOL) { LGNN_TB_D(LGNN_GRAD_POOL, LGNN_ACT_NONE) }
-    else { LGNN_TB_D(LGNN_GRAD_TRANSPOSE, LGNN_ACT_NONE) }
-  }
-#undef LGNN_TB_D
-#undef LGNN_TB
-  return hipGetLastError();
+  one_of<LGNN_GRAD_TRANSPOSE, LGNN_GRAD_DIRECT, LGNN_GRAD_POOL>(grad_mode, [&](auto GM) {
+    one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+      one_of<false, true>(dXpre != nullptr, [&](auto D) {
+        enqueue(k_bwd<GM, A, D>, grid, dim3(NT), s, dY, batch, gptr, pool_mean, tptr, tidx, tw,
+                tself, H, X, M, K, W, N, dXpre, dWp, dbp, tile_mask, want, accumulate, BnFuse{},
+                nullptr, nullptr, 0);
+      });
+    });
+  });
+  return last_error();
 }
 
-// ------------------------------------------------------------------------------------------
-// C ABI: fused GCN stack forward
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // C ABI: layer-wise linear kernels with BatchNorm folded in (the GIN MLP)
 // ------------------------------------------------------------------------------------------
@@ -745,24 +728,17 @@ extern "C" int lgnn_node_linear_fwd_bn(const float* X, int64_t M, int K, const i
   }
   const dim3 grid((unsigned)P);  // the stats need one partial row per workgroup
   float* So = rowptr ? S_out : nullptr;
-#define LGNN_TFB(G, A, BM)                                                                      \
-  hipLaunchKernelGGL((k_fwd<G, A, BM>), grid, dim3(NT), 0, s, X, M, K, rowptr, col, w,        \
-                     self_scale, W, b, N, Y, So, nullptr, 0, bn)
-  if (stats) {
-    if (rowptr) {
-      if (act == LGNN_ACT_ELU) LGNN_TFB(true, LGNN_ACT_ELU, BN_STATS);
-      else LGNN_TFB(true, LGNN_ACT_NONE, BN_STATS);
-    } else {
-      if (act == LGNN_ACT_ELU) LGNN_TFB(false, LGNN_ACT_ELU, BN_STATS);
-      else LGNN_TFB(false, LGNN_ACT_NONE, BN_STATS);
-    }
-  } else {
-    if (act == LGNN_ACT_ELU) LGNN_TFB(false, LGNN_ACT_ELU, BN_IN);
-    else LGNN_TFB(false, LGNN_ACT_NONE, BN_IN);
-  }
-#undef LGNN_TFB
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_EINVAL;
+  one_of<BN_IN, BN_STATS>(stats ? BN_STATS : BN_IN, [&](auto BM) {
+    one_of<false, true>(rowptr != nullptr, [&](auto G) {
+      one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+        if constexpr (BM == BN_STATS || !G)  // BN_IN never gathers (refused above)
+          r = launch(k_fwd<G, A, BM>, grid, dim3(NT), s, X, M, K, rowptr, col, w, self_scale, W, b,
+                     N, Y, So, nullptr, 0, bn);
+      });
+    });
+  });
+  return r;
 }
 
 extern "C" int lgnn_node_linear_bwd_bn(int bn_mode, const float* dY, const float* H, int act,
@@ -822,37 +798,31 @@ static int node_linear_bwd_bn_impl(
     return LGNN_OK;
   }
   const dim3 grid((unsigned)num_partials);
-#define LGNN_TBB(AC, D, BM)                                                                     \
-  hipLaunchKernelGGL((k_bwd<LGNN_GRAD_DIRECT, AC, D, BM>), grid, dim3(NT), 0, s, dY, nullptr,  \
-                     nullptr, 0, nullptr, nullptr, nullptr, 0.f, H, X, M, K, W, N, dXpre,      \
-                     dW_partial, db_partial, nullptr, 0, 0, bn)
-#define LGNN_TBP(AC)                                                                            \
-  hipLaunchKernelGGL((k_bwd<LGNN_GRAD_POOL, AC, true, BN_GSTATS>), grid, dim3(NT), 0, s, nullptr, \
-                     batch, gptr, pool_mean, nullptr, nullptr, nullptr, 0.f, H, X, M, K, W, N,    \
-                     dXpre, dW_partial, db_partial, nullptr, 0, 0, bn, dlogits, Wout,           \
-                     num_classes)
-#define LGNN_TBT(AC)                                                                            \
-  hipLaunchKernelGGL((k_bwd<LGNN_GRAD_TRANSPOSE, AC, true, BN_GSTATS>), grid, dim3(NT), 0, s, dY, \
-                     nullptr, nullptr, 0, tptr, tidx, tw, tself, H, X, M, K, W, N, dXpre,        \
-                     dW_partial, db_partial, nullptr, 0, 0, bn)
-  if (pool) {  // the pooled-output gradient formed from dlogits and out_proj's W (no dH tensor)
-    if (act == LGNN_ACT_ELU) LGNN_TBP(LGNN_ACT_ELU);
-    else LGNN_TBP(LGNN_ACT_NONE);
-  } else if (tptr) {  // dY = tself dS + A^T dS gathered through the transpose CSR as loaded
-    if (act == LGNN_ACT_ELU) LGNN_TBT(LGNN_ACT_ELU);
-    else LGNN_TBT(LGNN_ACT_NONE);
-  } else if (bn_mode == BN_GSTATS) {
-    if (act == LGNN_ACT_ELU) LGNN_TBB(LGNN_ACT_ELU, true, BN_GSTATS);
-    else LGNN_TBB(LGNN_ACT_NONE, true, BN_GSTATS);
-  } else {
-    if (dXpre) LGNN_TBB(LGNN_ACT_NONE, true, BN_GIN);
-    else LGNN_TBB(LGNN_ACT_NONE, false, BN_GIN);
+  const dim3 block(NT);
+  int r = LGNN_OK;
+  if (bn_mode == BN_GIN) {  // no activation, never pooled or gathered (checked above)
+    one_of<false, true>(dXpre != nullptr, [&](auto D) {
+      r = launch(k_bwd<LGNN_GRAD_DIRECT, LGNN_ACT_NONE, D, BN_GIN>, grid, block, s, dY, nullptr,
+                 nullptr, 0, nullptr, nullptr, nullptr, 0.f, H, X, M, K, W, N, dXpre, dW_partial,
+                 db_partial, nullptr, 0, 0, bn, nullptr, nullptr, 0);
+    });
+    return r;
   }
-#undef LGNN_TBB
-#undef LGNN_TBP
-#undef LGNN_TBT
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  one_of<LGNN_ACT_NONE, LGNN_ACT_ELU>(act, [&](auto A) {
+    if (pool)  // the pooled-output gradient formed from dlogits and out_proj's W (no dH tensor)
+      r = launch(k_bwd<LGNN_GRAD_POOL, A, true, BN_GSTATS>, grid, block, s, nullptr, batch, gptr,
+                 pool_mean, nullptr, nullptr, nullptr, 0.f, H, X, M, K, W, N, dXpre, dW_partial,
+                 db_partial, nullptr, 0, 0, bn, dlogits, Wout, num_classes);
+    else if (tptr)  // dY = tself dS + A^T dS gathered through the transpose CSR as loaded
+      r = launch(k_bwd<LGNN_GRAD_TRANSPOSE, A, true, BN_GSTATS>, grid, block, s, dY, nullptr,
+                 nullptr, 0, tptr, tidx, tw, tself, H, X, M, K, W, N, dXpre, dW_partial,
+                 db_partial, nullptr, 0, 0, bn, nullptr, nullptr, 0);
+    else
+      r = launch(k_bwd<LGNN_GRAD_DIRECT, A, true, BN_GSTATS>, grid, block, s, dY, nullptr, nullptr,
+                 0, nullptr, nullptr, nullptr, 0.f, H, X, M, K, W, N, dXpre, dW_partial,
+                 db_partial, nullptr, 0, 0, bn, nullptr, nullptr, 0);
+  });
+  return r;
 }
 
 extern "C" int lgnn_node_linear_bwd_bn_pool(
@@ -897,10 +867,7 @@ extern "C" int lgnn_tile_open(const int32_t* rowptr, const int32_t* col, int64_t
   if (ntiles == 0) return LGNN_OK;
   int64_t g = (M + lgnn_tile::NT - 1) / lgnn_tile::NT;
   if (g > 4096) g = 4096;
-  hipLaunchKernelGGL(lgnn_tile::k_tile_open, dim3((unsigned)g), dim3(lgnn_tile::NT), 0, s, rowptr,
-                     col, M, open);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  return launch(k_tile_open, dim3((unsigned)g), dim3(NT), s, rowptr, col, M, open);
 }
 
 extern "C" int lgnn_gcn_stack_fwd(const float* X, int64_t M, int d_in, int has_in_proj,
@@ -929,14 +896,11 @@ extern "C" int lgnn_gcn_stack_fwd(const float* X, int64_t M, int d_in, int has_i
   const int64_t ntiles = (M + lgnn_tile::TM - 1) / lgnn_tile::TM;
   dim3 grid((unsigned)(ntiles < 512 ? ntiles : 512));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (has_in_proj)
-    hipLaunchKernelGGL(lgnn_tile::k_stack_fwd<true>, grid, dim3(lgnn_tile::NT), 0, s, X, M,
-                       rowptr, col, w, L, a, tile_open);
-  else
-    hipLaunchKernelGGL(lgnn_tile::k_stack_fwd<false>, grid, dim3(lgnn_tile::NT), 0, s, X, M,
-                       rowptr, col, w, L, a, tile_open);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_OK;
+  one_of<false, true>(has_in_proj != 0, [&](auto IN) {
+    r = launch(k_stack_fwd<IN>, grid, dim3(NT), s, X, M, rowptr, col, w, L, a, tile_open);
+  });
+  return r;
 }
 
 #ifdef LGNN_STAMPS
@@ -986,12 +950,10 @@ extern "C" int lgnn_gcn_stack_bwd(const float* dP, const int64_t* batch, const i
     return LGNN_OK;
   }
   dim3 grid((unsigned)num_partials);
-  if (L == 1)
-    hipLaunchKernelGGL(lgnn_tile::k_stack_bwd<2>, grid, dim3(lgnn_tile::NTB), 0, s, dP, batch, gptr,
-                       pool_mean, rowptr, col, w, M, a, tile_open);
-  else
-    hipLaunchKernelGGL(lgnn_tile::k_stack_bwd<3>, grid, dim3(lgnn_tile::NTB), 0, s, dP, batch, gptr,
-                       pool_mean, rowptr, col, w, M, a, tile_open);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? LGNN_OK : (int)e;
+  int r = LGNN_OK;
+  one_of<3, 2>(L + 1, [&](auto NL) {
+    r = launch(k_stack_bwd<NL>, grid, dim3(NTB), s, dP, batch, gptr, pool_mean, rowptr, col, w, M,
+               a, tile_open);
+  });
+  return r;
 }

@@ -75,6 +75,10 @@ def test_weight_prep_bitexact(cuda, N, K):
     (65, 1, 128, False, True),         # K = 1
     (1, 1025, 128, False, False),
     (63, 200, 96, True, True),
+    # lgnn_bf16_gemm's (fp32 rows, K % 4 == 0, 64-wide K chunks) arms the shapes above leave out:
+    # two chunks unvectorised, and seventeen vectorised
+    (70, 126, 128, False, True),
+    (70, 1028, 128, False, False),
 ])
 def test_gemm_vs_rounded_product(cuda, M, K, N, a_bf16, bias):
     g = torch.Generator().manual_seed(M + K + N)
@@ -98,6 +102,14 @@ def test_gemm_vs_rounded_product(cuda, M, K, N, a_bf16, bias):
     (130, 33, 62, False),
     (1, 1025, 128, False),
     (0, 128, 128, True),
+    # lgnn_bf16_wgrad picks k_bf_wgrad<x is fp32, chunks per split> from M and K (bflin.hip wg_cpb:
+    # the smallest of 3, 6, 12, 24 that keeps 17 k-blocks x splits within 480 workgroups). Above:
+    # (fp32, 24), (bf16, 3), (fp32, 3). Here 6 and 12 for both, and (bf16, 24), at the smallest M.
+    (5400, 1025, 8, False),
+    (10800, 1025, 8, False),
+    (5400, 1026, 8, True),
+    (10800, 1026, 8, True),
+    (42279, 1026, 8, True),
 ])
 def test_wgrad_vs_rounded_product(cuda, M, K, N, x_bf16):
     g = torch.Generator().manual_seed(M * 7 + K + N)

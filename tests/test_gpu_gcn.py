@@ -10,7 +10,7 @@ import torch
 import oracle.pyg_ref as ref
 from lesion_gnn_amd import _lib, ops, synth
 from lesion_gnn_amd.conv import GCNConv, global_add_pool, global_mean_pool
-from lesion_gnn_amd.graph import Graph
+from lesion_gnn_amd.graph import NO_CSR, Graph
 from lesion_gnn_amd.models.gcn import GCN
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +127,87 @@ def test_node_linear_bwd(cuda, M, K, N, gather):
     torch.testing.assert_close(bg.grad.cpu(), b.grad, atol=1e-4, rtol=1e-4)
     if N <= 128:
         torch.testing.assert_close(xg.grad.cpu(), x.grad, atol=1e-4, rtol=1e-4)
+
+
+# lgnn_node_linear_fwd / _bwd at the C ABI, one case per template instantiation their launch sites
+# can pick (node.hip's generic kernels, tile.hip's k_fwd / k_bwd): 70 rows (a full 64-row tile and
+# a partial one), K = 132 or 37 off the 128-wide tile path (37 is the K % 4 != 0 form), K = 128 on
+# it, N = 4, or 132 where dX needs its own launch.
+ARM_M = 70
+ARM_SIZES = [30, 25, 15]  # the graphs POOL mode broadcasts over
+
+
+def _arm_graph(cuda):
+    bt = synth.make_batch(2, k=6, seed=3, sizes="lognormal")
+    ei = bt.edge_index[:, bt.edge_index.max(0).values < ARM_M]
+    e, w = ref.gcn_norm(ei, ARM_M)
+    agg = lambda t: ref.scatter_sum(w.view(-1, 1) * t.index_select(0, e[0]), e[1], ARM_M)
+    return Graph(ei.to(cuda), ARM_M).csr("gcn"), agg
+
+
+@pytest.mark.parametrize("act", [_lib.LGNN_ACT_NONE, _lib.LGNN_ACT_ELU], ids=["none", "elu"])
+@pytest.mark.parametrize("K,gather", [(37, False), (132, False), (132, True), (128, False),
+                                      (128, True)],
+                         ids=["scalar", "vec", "gather", "tile", "tile_gather"])
+def test_node_linear_fwd_arms(cuda, K, gather, act):
+    """lgnn_node_linear_fwd off the tile path: k_linear_fwd<gather, K % 4 == 0, act>; at K = 128
+    on it: tile.hip's k_fwd<gather, act>."""
+    torch.manual_seed(K + act)
+    M, N = ARM_M, 4
+    x, W, b = torch.randn(M, K), torch.randn(N, K) / K ** 0.5, torch.randn(N)
+    c, agg = _arm_graph(cuda) if gather else (NO_CSR, lambda t: t)
+    z = agg(x) @ W.T + b
+    want = torch.nn.functional.elu(z) if act == _lib.LGNN_ACT_ELU else z
+    y = torch.empty(M, N, device=cuda)
+    _lib.call("lgnn_node_linear_fwd", x.to(cuda), M, K, c.rowptr, c.col, c.w, 0.0, W.to(cuda),
+              b.to(cuda), N, act, y, None, _lib.stream(cuda))
+    torch.testing.assert_close(y.cpu(), want, atol=1e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize("dx", ["none", "fused", "own_launch"])
+@pytest.mark.parametrize("gather", [False, True], ids=["plain", "gather"])
+@pytest.mark.parametrize("act", [_lib.LGNN_ACT_NONE, _lib.LGNN_ACT_ELU], ids=["none", "elu"])
+@pytest.mark.parametrize("mode", [_lib.LGNN_GRAD_DIRECT, _lib.LGNN_GRAD_POOL,
+                                  _lib.LGNN_GRAD_TRANSPOSE], ids=["direct", "pool", "transpose"])
+@pytest.mark.parametrize("K", [132, 128])
+def test_node_linear_bwd_arms(cuda, K, mode, act, gather, dx):
+    """lgnn_node_linear_bwd off the tile path (K = 132; a gathered backward and N = 132 at any K):
+    k_linear_bwd<mode, act, gather, dX in the kernel> and, where N > 128 gives dX its own launch,
+    k_linear_dx<mode, act>. At K = 128, N = 4 without gather it is tile.hip's
+    k_bwd<mode, act, dX>. Each argument changes the expected dW, db or dX, so two of them swapped
+    at the launch site fail here. The transpose structure of TRANSPOSE mode is the graph's own CSR
+    (the entry only walks it)."""
+    torch.manual_seed(100 * mode + 10 * act + gather)
+    M, N = ARM_M, (132 if dx == "own_launch" else 4)
+    B = len(ARM_SIZES)
+    c, agg = _arm_graph(cuda)
+    x, W = torch.randn(M, K), torch.randn(N, K) / K ** 0.5
+    H = torch.randn(M, N)  # the saved output: only its sign and value enter, through ELU'
+    batch = torch.repeat_interleave(torch.arange(B), torch.tensor(ARM_SIZES))
+    gptr = torch.tensor([0, 30, 55, 70], dtype=torch.int32)
+    pool_mean, tself = int(act == _lib.LGNN_ACT_ELU), 0.5
+    if mode == _lib.LGNN_GRAD_POOL:
+        dY = torch.randn(B, N)
+        G = dY[batch] / (torch.tensor(ARM_SIZES, dtype=torch.float32)[batch].view(-1, 1)
+                         if pool_mean else 1.0)
+    else:
+        dY = torch.randn(M, N)
+        G = tself * dY + agg(dY) if mode == _lib.LGNN_GRAD_TRANSPOSE else dY
+    dZ = G * torch.where(H > 0, torch.ones_like(H), H + 1) if act == _lib.LGNN_ACT_ELU else G
+    want_dW, want_db, want_dX = dZ.T @ (agg(x) if gather else x), dZ.sum(0), dZ @ W
+    g = c if gather else NO_CSR
+    t = c if mode == _lib.LGNN_GRAD_TRANSPOSE else NO_CSR
+    P = _lib.query("lgnn_bwd_num_partials", M, N, K, int(gather))
+    dWp = torch.full((P, N, K), float("nan"), device=cuda)
+    dbp = torch.full((P, N), float("nan"), device=cuda)
+    dX = torch.full((M, K), float("nan"), device=cuda) if dx != "none" else None
+    _lib.call("lgnn_node_linear_bwd", mode, dY.to(cuda), batch.to(cuda), gptr.to(cuda), pool_mean,
+              t.rowptr, t.col, t.w, tself, H.to(cuda), act, x.to(cuda), M, K, g.rowptr, g.col, g.w,
+              0.0, W.to(cuda), N, dX, dWp, dbp, P, _lib.stream(cuda))
+    torch.testing.assert_close(dWp.sum(0).cpu(), want_dW, atol=1e-4, rtol=1e-4)
+    torch.testing.assert_close(dbp.sum(0).cpu(), want_db, atol=1e-4, rtol=1e-4)
+    if dX is not None:
+        torch.testing.assert_close(dX.cpu(), want_dX, atol=1e-4, rtol=1e-4)
 
 
 def make_pair(hidden, d_in=128, classes=5, pool="mean", seed=1234):

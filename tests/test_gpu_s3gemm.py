@@ -35,6 +35,13 @@ def _mag(A, B):
 
 SHAPES = [(42279, 1025, 128), (1000, 1025, 128), (333, 256, 512), (130, 37, 300), (64, 128, 256),
           (7, 5, 3), (257, 64, 130)]
+# lgnn_s3_gemm picks k_s3_gemm<planes, K % 4 == 0, chunks> from K alone (64-wide K chunks; 2, 4, 8
+# and 17 of them have unrolled bodies, every other count runs the pair loop): one shape per
+# (vectorised, chunks) pair the shapes above leave out, at M = 70 (a full 64-row tile and a partial
+# one) and a narrow N. Reached there: K = 1025 (no, 17), 256 (yes, 4), 128 (yes, 2), 64 (yes, loop),
+# 37 and 5 (no, loop).
+ARM_SHAPES = [(70, 512, 4), (70, 1028, 4), (70, 126, 4), (70, 254, 4), (70, 510, 4), (70, 192, 4)]
+SHAPES += ARM_SHAPES
 
 
 @pytest.mark.parametrize("M,K,N", SHAPES)
@@ -72,7 +79,8 @@ def test_s3_wgrad_and_bias_grad(cuda, M, K, N):
     assert torch.equal(again, dW)  # fixed-order reduction: deterministic
 
 
-@pytest.mark.parametrize("M,K,N", [(1000, 1025, 128), (333, 256, 512), (130, 37, 300)])
+@pytest.mark.parametrize("M,K,N", [(1000, 1025, 128), (333, 256, 512), (130, 37, 300),
+                                   (70, 128, 4), (70, 64, 4)] + ARM_SHAPES)
 def test_bf16_plane_mode(cuda, M, K, N):
     """planes = 1: bf16 RNE operands (torch's .to(bfloat16)), fp32 accumulation — the bf16 GEMM
     semantics of the oracle's _Bf16Linear, for widths the bf16 tile kernel does not take."""
@@ -183,7 +191,9 @@ def test_gat_weight_bundle_bitwise(cuda, monkeypatch, compiled):
         assert torch.equal(res[0][1][n], res[1][1][n]), n
 
 
-@pytest.mark.parametrize("heads,C,K", [(2, 64, 1025), (4, 32, 128), (1, 128, 128), (8, 8, 37)])
+@pytest.mark.parametrize("heads,C,K", [(2, 64, 1025), (4, 32, 128), (1, 128, 128), (8, 8, 37),
+                                       # the (K % 4 == 0, chunks) arms those leave out
+                                       (2, 8, 1028), (2, 8, 126), (2, 8, 64)])
 def test_s3_gemm_att_scores(cuda, heads, C, K):
     """lgnn_s3_gemm_att (the fp32 GATConv.lin with the attention scores in its epilogue): Y equals
     lgnn_s3_gemm's bit for bit, and a_s / a_d (one fmaf chain per row and head) match

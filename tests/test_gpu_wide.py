@@ -88,6 +88,26 @@ def test_wide_linear_elu_and_act_bwd(cuda, M, K, N):
     assert torch.equal(dz.cpu(), want_dz)
 
 
+@pytest.mark.parametrize("K", [126, 510, 37, 64])
+def test_s3_gemm_act_other_k_arms(cuda, K):
+    """lgnn_s3_gemm_act picks k_s3_gemm<3, K % 4 == 0, chunks, false, ELU> from K (64-wide chunks;
+    2 and 8 of them unrolled). The model reaches it at multiples of 4 only (test above: 2, 4 -> the
+    pair loop, 8 chunks). Here, at the C ABI: 2 and 8 chunks and the pair loop with K % 4 != 0, and
+    the one-chunk pair loop; 70 rows (a full tile and a partial one), same reference and bar."""
+    g = torch.Generator().manual_seed(K)
+    M, N = 70, 4
+    x = torch.randn(M, K, generator=g)
+    W = torch.randn(N, K, generator=g) / K ** 0.5
+    b = torch.randn(N, generator=g)
+    xc, bc = x.to(cuda), b.to(cuda)
+    Wp = ops.dense_planes(W.to(cuda), False, False)
+    y = torch.empty(M, N, device=cuda)
+    _lib.call("lgnn_s3_gemm_act", _lib.ptr(xc), M, K, _lib.ptr(Wp), N, _lib.ptr(bc),
+              _lib.LGNN_ACT_ELU, _lib.ptr(y), _lib.stream(cuda))
+    want = torch.nn.functional.elu(x.double() @ W.double().T + b.double())
+    torch.testing.assert_close(y.cpu().double(), want, rtol=0, atol=2e-5)
+
+
 @pytest.mark.parametrize("D", [4, 64, 128, 200, 512])
 def test_spmm_tiles_closed_open_and_partial(cuda, D):
     """lgnn_spmm stages a 64-row tile in LDS when none of its CSR entries leaves it and gathers
