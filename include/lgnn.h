@@ -1491,6 +1491,55 @@ int lgnn_sift_gather(int batch, int num_candidates, const int64_t* node_ptr, int
 int lgnn_sift_descriptors(const float* gauss, int batch, int height, int width, const float* kf,
                           const int32_t* ki, int num_nodes, float* x, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fundus image preprocessing for a batch of uint8 RGB images of any sizes. Replaces the chain
+ * FundusAutocrop -> LongestMaxSize -> PadIfNeeded(BORDER_CONSTANT) -> Normalize -> ToTensorV2 of
+ * the reference (fundus_datamodules/base.py:93-120, utils/autocrop.py:28-45;
+ * lesion_gnn/datasets/nodes/lesions.py:132-141), with OpenCV's 8-bit INTER_LINEAR and
+ * INTER_NEAREST restated in integers (tests/fundus_ref.py states the arithmetic,
+ * parity with OpenCV itself is not pinned). The entries are additions: every earlier signature
+ * is unchanged, so the ABI version stays.
+ *   images, masks: HOST arrays of `batch` device pointers, image b [heights[b], widths[b], 3] and
+ *   mask b [heights[b], widths[b]] uint8, contiguous, at any byte alignment; heights, widths:
+ *   host arrays. The tables are read during the call and packed into kernel arguments,
+ *   LGNN_FUNDUS_MAX_IMAGES images per launch. No device allocation, no host read: capturable.
+ *   LGNN_EINVAL, before any launch: batch < 1, a side outside [2, LGNN_FUNDUS_MAX_SIDE], size
+ *   outside [2, LGNN_FUNDUS_MAX_SIDE], a std that is not > 0, a non-finite mean, a NULL table,
+ *   image or required output, out and out_u8 both NULL, out_mask without masks (or a NULL mask
+ *   among them).
+ * lgnn_fundus_bbox: boxes [batch, 4] int32 (x_min, x_max, y_min, y_max): the extreme coordinates
+ *   of the pixels with red > threshold (strict; a NaN threshold lights nothing), or (0, W, 0, H)
+ *   when there is none or x_min == x_max or y_min == y_max. The crop image[y_min:y_max,
+ *   x_min:x_max] excludes the last lit row and column, as the reference's does. One launch that
+ *   zeroes the accumulators, then two per LGNN_FUNDUS_MAX_IMAGES images: a workgroup takes a
+ *   contiguous share of lgnn_fundus_bbox_share(H, W) 16-pixel groups of its image (int32
+ *   atomicMax across workgroups: order-free, so two calls give the same bits).
+ * lgnn_fundus_bbox_share: that share for a height x width image, in 16-pixel groups counted from
+ *   the image's first 16-byte-aligned byte: workgroup b reads groups [b * share, (b + 1) * share).
+ *   0 for a side outside [2, LGNN_FUNDUS_MAX_SIDE]. A query: nothing is launched.
+ * lgnn_fundus_preprocess: per image, from boxes[b] on the device: h = y_max - y_min, w = x_max -
+ *   x_min; scale = size / double(max(h, w)); new_h = max(1, rint(h * scale)), new_w likewise
+ *   (half to even, in double); the crop resized to new_h x new_w (INTER_LINEAR; the mask
+ *   INTER_NEAREST); centred in size x size with pad_top = (size - new_h) / 2, pad_left likewise
+ *   and the remainder below and right, padding 0; out[c][y][x] = (float(v) - m_c) * r_c with
+ *   m_c = float(mean_c * 255), r_c = float(1 / (std_c * 255)) (products in double on the host).
+ *   Nullable outputs: out [batch, 3, size, size] fp32, out_u8 [batch, size, size, 3] uint8
+ *   (before the normalisation), out_mask [batch, size, size] uint8, geom [batch, 8] int32
+ *   (x_min, y_min, w, h, new_w, new_h, pad_left, pad_top). boxes entries outside their image are
+ *   clamped into it (no read outside an image whatever boxes holds). One launch per
+ *   LGNN_FUNDUS_MAX_IMAGES images.
+ * ------------------------------------------------------------------------------------------- */
+#define LGNN_FUNDUS_MAX_SIDE 16384
+#define LGNN_FUNDUS_MAX_IMAGES 16
+int lgnn_fundus_bbox_share(int height, int width);
+int lgnn_fundus_bbox(int batch, const uint8_t* const* images, const int* heights,
+                     const int* widths, float threshold, int32_t* boxes, void* stream);
+int lgnn_fundus_preprocess(int batch, const uint8_t* const* images, const uint8_t* const* masks,
+                           const int* heights, const int* widths, const int32_t* boxes, int size,
+                           double mean0, double mean1, double mean2, double std0, double std1,
+                           double std2, float* out, uint8_t* out_u8, uint8_t* out_mask,
+                           int32_t* geom, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

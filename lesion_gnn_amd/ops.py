@@ -2877,6 +2877,86 @@ def sift_descriptors(pyramid: SiftPyramid, kf: torch.Tensor, ki: torch.Tensor) -
 
 
 # ----------------------------------------------------------------------------------------------
+# Fundus image preprocessing (fundus.hip): autocrop box, resize, pad, normalise for a batch of
+# images of different sizes
+# ----------------------------------------------------------------------------------------------
+
+
+def _fundus_images(images, what: str = "images", channels: int | None = 3) -> list[torch.Tensor]:
+    """A (B, H, W, 3) uint8 tensor or a list of (H_b, W_b, 3) uint8 tensors -> the contiguous
+    per-image tensors (views where the input already is contiguous). channels None: (H, W)
+    label masks."""
+    shape = "(H, W, 3)" if channels else "(H, W)"
+    imgs = list(images.unbind(0)) if isinstance(images, torch.Tensor) and \
+        images.dim() == (4 if channels else 3) else images
+    if isinstance(imgs, torch.Tensor) or len(imgs) == 0:
+        raise ValueError(f"{what} must be a batch or a non-empty list of {shape} uint8 tensors")
+    for t in imgs:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"{what} must be uint8 tensors, got "
+                             f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dim() != (3 if channels else 2) or (channels and t.size(2) != channels):
+            raise ValueError(f"each of {what} must be {shape}, got {tuple(t.shape)}")
+    _lib.require_gpu(*imgs)
+    side = _lib.LGNN_FUNDUS_MAX_SIDE
+    for t in imgs:
+        if not (2 <= t.size(0) <= side and 2 <= t.size(1) <= side):
+            raise ValueError(f"each of {what} must have sides in [2, {side}], got "
+                             f"{tuple(t.shape)}")
+    return [t.contiguous() for t in imgs]
+
+
+def fundus_bbox(images, threshold: float = 25.0) -> torch.Tensor:
+    """images: a (B, H, W, 3) uint8 tensor or a list of (H_b, W_b, 3) uint8 tensors of any sizes
+    -> boxes (B, 4) int32 (x_min, x_max, y_min, y_max): the extreme coordinates of the pixels with
+    red > threshold, or (0, W, 0, H) for an image with none or with x_min == x_max or y_min ==
+    y_max (lgnn_fundus_bbox). No host read; two launches per 16 images."""
+    imgs = _fundus_images(images)
+    dev = imgs[0].device
+    boxes = torch.empty(len(imgs), 4, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_fundus_bbox", len(imgs), imgs, [t.size(0) for t in imgs],
+              [t.size(1) for t in imgs], float(threshold), boxes, _s(dev))
+    return boxes
+
+
+def fundus_preprocess(images, boxes: torch.Tensor, size: int, mean, std, masks=None,
+                      want_float: bool = True, want_uint8: bool = False):
+    """The crop boxes[b] of image b resized so that its longer side is `size` (8-bit INTER_LINEAR
+    restated in integers; the label mask INTER_NEAREST), centred in size x size on zeros and
+    normalised -> (image (B, 3, size, size) fp32 or None, uint8 (B, size, size, 3) or None, mask
+    (B, size, size) uint8 or None, geom (B, 8) int32: x_min, y_min, w, h, new_w, new_h, pad_left,
+    pad_top) (lgnn_fundus_preprocess). images / masks as `fundus_bbox` takes them, masks (H_b,
+    W_b) uint8. No host read; one launch per 16 images."""
+    imgs = _fundus_images(images)
+    B = len(imgs)
+    dev = imgs[0].device
+    S = int(size)
+    if not 2 <= S <= _lib.LGNN_FUNDUS_MAX_SIDE:
+        raise ValueError(f"size must be in [2, {_lib.LGNN_FUNDUS_MAX_SIDE}], got {size}")
+    if not (want_float or want_uint8):
+        raise ValueError("fundus_preprocess: at least one of want_float and want_uint8")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3 or not all(s > 0 for s in std):
+        raise ValueError("mean and std are three numbers each, every std positive")
+    _lib.require_gpu(boxes)
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, 4):
+        raise ValueError(f"boxes must be ({B}, 4) int32")
+    mks = None
+    if masks is not None:
+        mks = _fundus_images(masks, "masks", None)
+        if [tuple(m.shape) for m in mks] != [tuple(t.shape[:2]) for t in imgs]:
+            raise ValueError("masks must match the images' heights and widths")
+    out = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev) if want_float else None
+    u8 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev) if want_uint8 else None
+    om = torch.empty(B, S, S, dtype=torch.uint8, device=dev) if mks is not None else None
+    geom = torch.empty(B, 8, dtype=torch.int32, device=dev)
+    _lib.call("lgnn_fundus_preprocess", B, imgs, mks, [t.size(0) for t in imgs],
+              [t.size(1) for t in imgs], boxes.contiguous(), S, *mean, *std, out, u8, om, geom,
+              _s(dev))
+    return out, u8, om, geom
+
+
+# ----------------------------------------------------------------------------------------------
 # Set attention (setattn.hip): segmented multi-head attention over ragged sets, the residual +
 # activation + LayerNorm of PyG's MultiheadAttentionBlock, the set readout
 # ----------------------------------------------------------------------------------------------
